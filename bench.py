@@ -8,6 +8,11 @@ Contract: `python bench.py --gpus N --steps K --warmup W`.  For N > 1 either lau
 rank per GPU, RCCL; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or run it directly: the parent then
 starts the N ranks itself as fresh child processes BEFORE touching the GPU, relays rank 0's JSON line and exits non-zero
 if any rank failed.  Weak scaling (per-GPU batch fixed).  Rank 0 prints ONE JSON line.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the JSON line.  `--full` adds what takes
+runs of its own: the per-kernel roofline table (an eager re-issue of the step after the timed region, joined to the committed
+profiles) and the CPU-oracle baseline.  `--dump-outputs DIR`, after the timed steps, replays the captured step on the last
+timed batch for a fresh model primed from the seeded initial state into a state every run reproduces, and writes what
+that step computed as DIR/<name>.npy.
 """
 import argparse
 import copy
@@ -238,6 +243,87 @@ def pmc_traffic(symbols):
     return round(tot / n) if n else None
 
 
+def roofline_report(prof, prof_steps, step_ms, reissued):
+    """--full: the `roofline` object of the JSON line from the HIP-event timings `prof` of `prof_steps` steps."""
+    # ---- per-kernel roofline (north_star: GB/s for the mel / augment kernels, TFLOP/s for the encoder GEMMs); the headline
+    #      `roofline` object = the row with the largest share of the step (the dominant kernel), named by its rocprofv3 symbol
+    per_kernel = per_kernel_report(prof, prof_steps, step_ms)
+    # Which kernel is "the dominant one": the top row of the committed rocprofv3 summary of this same command (kernel time inside
+    # the replayed graph) when one exists and this run launched that kernel; otherwise the live row with the largest share.  All
+    # live rows that launch that kernel symbol (e.g. the heads' weight gradients AND the Barlow correlation: the same
+    # instantiation) are merged into the headline.
+    rows = [r for r in per_kernel if r.get("bound")]
+    csv_top = (in_graph_stats(["\0"]) or (None, 0, None, None))[3]
+    chosen, how = [], None
+    if csv_top:
+        chosen = [r for r in rows if any(sy in csv_top for sy in r["kernel_symbols"])]
+        how = "top row of the committed kernel_stats.csv"
+    if not chosen:
+        chosen, how = rows[:1], "largest share of the step in this run"
+    top = chosen[0]
+    symbols = sorted({sy for r in chosen for sy in r["kernel_symbols"] if not csv_top or sy in csv_top} or set(top["kernel_symbols"]))
+    n_l = sum(r["launches_per_step"] for r in chosen)
+    t_us = sum(r["avg_us"] * r["launches_per_step"] for r in chosen)
+    work = sum(r["work_per_launch"] * r["launches_per_step"] for r in chosen)
+    scale = 1e12 if top["bound"] == "mfma" else 1e9
+    achieved = work / (t_us * 1e-6) / scale
+    roofline = {"bound": top["bound"], "achieved": round(achieved, 1), "peak": top["peak"], "unit": top["unit"],
+                "frac": round(achieved / top["peak"], 4), "traffic": pmc_traffic(symbols), "kernel": symbols[0],
+                "entry": [r["entry"] for r in chosen], "selected_by": how, "launches_per_step": round(n_l, 2),
+                "avg_launch_us": round(t_us / n_l, 2), "work_per_launch": work / n_l,
+                "share_of_step": round(sum(r["share_of_step"] for r in chosen), 4),
+                "timed_on": "eager re-issue of the step after the timed region" if reissued else "the timed region"}
+    fused = [r for r in chosen if r.get("bytes_per_launch")]
+    if fused:
+        # some launches of the headline kernel also apply the optimiser's update to their result: their HBM side, for the reader who
+        # prices the kernel by flops alone
+        fb = sum(r["bytes_per_launch"] * r["launches_per_step"] for r in fused)
+        ft = sum(r["avg_us"] * r["launches_per_step"] for r in fused)
+        roofline["epilogue"] = {"what": fused[0]["epilogue"], "launches_per_step": round(sum(r["launches_per_step"] for r in fused), 2),
+                                "bytes_per_launch": fb / sum(r["launches_per_step"] for r in fused),
+                                "hbm_GBs": round(fb / (ft * 1e-6) / 1e9, 1), "hbm_frac": round(fb / (ft * 1e-6) / 1e9 / PEAK_HBM_GBS, 4)}
+    ig = in_graph_stats(symbols)
+    if ig is not None and ig[0]:
+        # the same algorithmic work over the average duration rocprofv3 saw for this kernel INSIDE the replayed graph
+        per_s = roofline["work_per_launch"] / (ig[0] * 1e-9)
+        roofline.update(frac_in_graph=round(per_s / (top["peak"] * scale), 4), in_graph_avg_us=round(ig[0] * 1e-3, 2),
+                        in_graph_source=ig[2], profile_top_kernel=ig[3])
+    for r in per_kernel:
+        r.pop("peak", None)
+    roofline["per_kernel"] = per_kernel[:32]
+    return roofline
+
+
+DUMP_STATE_CAP = 1 << 18       # --dump-outputs: elements written per state tensor / per view; larger ones as a fixed seeded
+DUMP_VIEW_CAP = 1 << 22        # sample (with these caps everything written stays below 64 MB whatever the batch)
+
+
+def _dump_array(t, cap):
+    """device tensor -> numpy float32 (float64 for integer counters): whole when it has at most `cap` elements, else its
+    flattened elements at the sorted distinct positions among `cap` draws of a generator with a fixed seed."""
+    t = t.detach()
+    t = t.float() if t.is_floating_point() else t.double()
+    if t.numel() > cap:
+        idx = np.unique(np.random.RandomState(0).randint(0, t.numel(), cap))
+        t = t.flatten()[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, loss, views, model, world):
+    """--dump-outputs: what one training step computed - its loss, the two augmented views it trained on, the keys it pushed
+    into the MoCo queue, and the model's state after its SGD / EMA update (every entry of state_dict: both encoders, the
+    heads, the BatchNorm statistics, the queue) - one DIR/<name>.npy per array."""
+    K, n = model.queue.shape[1], views[0].shape[0] * world
+    start = (int(model.queue_ptr) - n) % K                       # the step enqueued the n keys just before the write pointer
+    arrays = {"loss": _dump_array(loss.reshape(1), 1), "view_1": _dump_array(views[0], DUMP_VIEW_CAP),
+              "view_2": _dump_array(views[1], DUMP_VIEW_CAP), "keys": _dump_array(model.queue[:, start:start + n], DUMP_STATE_CAP)}
+    arrays.update(("state." + k, _dump_array(v, DUMP_STATE_CAP)) for k, v in model.state_dict().items())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB) to {path}", file=sys.stderr)
+
+
 def synth_waves(B, L, seed):
     """Seeded uniform noise x0.1 + 440 Hz + 3 kHz tones; last two clips: silence / full scale."""
     g = np.random.RandomState(seed)
@@ -300,6 +386,18 @@ def cpu_baseline(B, steps, queue):
             "sample": f"{steps} steps of batch {B} (log-mel + two views + delores_m fwd/bwd/SGD, queue {queue}), fp32, torch-CPU oracle"}
 
 
+def train_step(model, opt, gstep, img_1, img_2, i):
+    """One training step on the two views: a replay of the captured step (its first calls run eagerly), or kernel by kernel."""
+    if gstep is not None:
+        return gstep(img_1, img_2)
+    opt.zero_grad()
+    loss = model.training_step((img_1, img_2), i)
+    loss.backward()
+    model.all_reduce_grads()
+    opt.step()
+    return loss
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (this process never touches the GPU and
     is not replaced), stream their stderr through, print rank 0's stdout (the JSON line), return the worst exit code."""
@@ -342,6 +440,10 @@ def main():
     ap.add_argument("--h2d", action="store_true", help="upload a fresh pinned host batch (B x 16000 fp32) every step on a copy stream, "
                     "two batches ahead of the training step, instead of re-using the batch resident in HBM (reported as "
                     "`h2d`; the contract's `value` is measured without it)")
+    ap.add_argument("--full", action="store_true", help="also report the per-kernel roofline (eager re-issue of the step after the "
+                    "timed region) and, on one rank, the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, replay the captured step on the last timed batch for "
+                    "a fresh model primed from the seeded initial state and write what it computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -376,8 +478,11 @@ def main():
     B = args.batch
     np.random.seed(31 + rank)
     random.seed(31 + rank)
-    torch.manual_seed(0)                                           # identical initial weights on every rank
-    model = Upstream_Expert(cfg, base_encoder=AudioNTT2020Task6, num_negatives=args.queue).to(dev).train()
+
+    def new_model():
+        torch.manual_seed(0)                                       # identical initial weights on every rank and in every run
+        return Upstream_Expert(cfg, base_encoder=AudioNTT2020Task6, num_negatives=args.queue).to(dev).train()
+    model = new_model()
     tfms = AugmentationModule(cfg, 100000, max_batch=B)
     front = UpstreamFrontEnd(cfg, tfms)
     opt = model.configure_optimizers()
@@ -421,20 +526,15 @@ def main():
         nxt[0] += 1
         return t
     ticket = [next_ticket()]
+    views = [None]                                                 # the views the latest step trained on (--dump-outputs)
 
     def step(i):
         # the front end of the NEXT batch is submitted (own stream) before this batch's training step is launched, so it
         # runs underneath it; every call does exactly one front end and one training step
         img_1, img_2 = front.collect(ticket[0])
+        views[0] = (img_1, img_2)
         ticket[0] = next_ticket()
-        if gstep is not None:
-            return gstep(img_1, img_2)
-        opt.zero_grad()
-        loss = model.training_step((img_1, img_2), i)
-        loss.backward()
-        model.all_reduce_grads()
-        opt.step()
-        return loss
+        return train_step(model, opt, gstep, img_1, img_2, i)
 
     if gstep is not None:
         for i in range(gstep.eager_steps + 1):                     # untimed: eager priming steps + the capture itself
@@ -445,7 +545,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    if gstep is None:
+    if gstep is None and args.full:
         N.PROFILE, N.PROFILE_ALL = {}, True
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -457,7 +557,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     final_loss = float(loss.detach())
-    if gstep is not None:
+    if args.full and gstep is not None:
         # kernels inside a replayed graph cannot carry HIP events: time the dominant kernel on an eager re-issue of the
         # very same step (same buffers, same streams) right after the timed region
         N.PROFILE, N.PROFILE_ALL = {}, True
@@ -470,6 +570,25 @@ def main():
     else:
         prof_steps = args.steps
     prof, N.PROFILE, N.PROFILE_ALL = N.PROFILE, None, False
+    if args.dump_outputs:
+        # The step's float atomics (BatchNorm statistics, weight gradients, split-K GEMMs) round differently from run to run and
+        # training compounds that step after step: identical runs end in states that differ by far more than rounding.  The
+        # dumped step is the timed path in its steady form - the replay of the captured step, with the momentum buffer, the fused
+        # weight-gradient + SGD GEMMs and a key encoder that lags the query encoder - run on the last timed batch by a fresh model
+        # whose two priming steps leave it in a state every run reproduces: the first one (learning rate 0) creates the momentum
+        # and the bf16 weight copies but keeps the seeded weights, the second moves the query encoder off the key encoder.
+        fresh = new_model()
+        fresh_opt = fresh.configure_optimizers()
+        fresh_g = None if gstep is None else fresh.graphed_step(fresh_opt, phases=args.graph_phases)
+        lr = fresh_opt.param_groups[0]["lr"]
+        fresh_opt.param_groups[0]["lr"] = 0.0
+        train_step(fresh, fresh_opt, fresh_g, *views[0], 0)
+        fresh_opt.param_groups[0]["lr"] = lr
+        train_step(fresh, fresh_opt, fresh_g, *views[0], 1)
+        fresh_loss = train_step(fresh, fresh_opt, fresh_g, *views[0], 2)     # graph path: captured, then replayed
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, fresh_loss, views[0], fresh, world)
     if rank == 0:
         print(f"[bench] gpu: {B * world * args.steps / dt:.1f} clips/s, {dt / args.steps * 1e3:.2f} ms/step "
               f"(host launch side {t_host / args.steps * 1e3:.2f} ms/step)", file=sys.stderr, flush=True)
@@ -480,52 +599,6 @@ def main():
     if rank != 0:
         return
 
-    # ---- per-kernel roofline (north_star: GB/s for the mel / augment kernels, TFLOP/s for the encoder GEMMs); the headline
-    #      `roofline` object = the row with the largest share of the step (the dominant kernel), named by its rocprofv3 symbol
-    per_kernel = per_kernel_report(prof, prof_steps, dt / args.steps * 1e3)
-    # Which kernel is "the dominant one": the top row of the committed rocprofv3 summary of this same command (kernel time inside
-    # the replayed graph) when one exists and this run launched that kernel; otherwise the live row with the largest share.  All
-    # live rows that launch that kernel symbol (e.g. the heads' weight gradients AND the Barlow correlation: the same
-    # instantiation) are merged into the headline.
-    rows = [r for r in per_kernel if r.get("bound")]
-    csv_top = (in_graph_stats(["\0"]) or (None, 0, None, None))[3]
-    chosen, how = [], None
-    if csv_top:
-        chosen = [r for r in rows if any(sy in csv_top for sy in r["kernel_symbols"])]
-        how = "top row of the committed kernel_stats.csv"
-    if not chosen:
-        chosen, how = rows[:1], "largest share of the step in this run"
-    top = chosen[0]
-    symbols = sorted({sy for r in chosen for sy in r["kernel_symbols"] if not csv_top or sy in csv_top} or set(top["kernel_symbols"]))
-    n_l = sum(r["launches_per_step"] for r in chosen)
-    t_us = sum(r["avg_us"] * r["launches_per_step"] for r in chosen)
-    work = sum(r["work_per_launch"] * r["launches_per_step"] for r in chosen)
-    scale = 1e12 if top["bound"] == "mfma" else 1e9
-    achieved = work / (t_us * 1e-6) / scale
-    roofline = {"bound": top["bound"], "achieved": round(achieved, 1), "peak": top["peak"], "unit": top["unit"],
-                "frac": round(achieved / top["peak"], 4), "traffic": pmc_traffic(symbols), "kernel": symbols[0],
-                "entry": [r["entry"] for r in chosen], "selected_by": how, "launches_per_step": round(n_l, 2),
-                "avg_launch_us": round(t_us / n_l, 2), "work_per_launch": work / n_l,
-                "share_of_step": round(sum(r["share_of_step"] for r in chosen), 4),
-                "timed_on": "eager re-issue of the step after the timed region" if gstep is not None else "the timed region"}
-    fused = [r for r in chosen if r.get("bytes_per_launch")]
-    if fused:
-        # some launches of the headline kernel also apply the optimiser's update to their result: their HBM side, for the reader who
-        # prices the kernel by flops alone
-        fb = sum(r["bytes_per_launch"] * r["launches_per_step"] for r in fused)
-        ft = sum(r["avg_us"] * r["launches_per_step"] for r in fused)
-        roofline["epilogue"] = {"what": fused[0]["epilogue"], "launches_per_step": round(sum(r["launches_per_step"] for r in fused), 2),
-                                "bytes_per_launch": fb / sum(r["launches_per_step"] for r in fused),
-                                "hbm_GBs": round(fb / (ft * 1e-6) / 1e9, 1), "hbm_frac": round(fb / (ft * 1e-6) / 1e9 / PEAK_HBM_GBS, 4)}
-    ig = in_graph_stats(symbols)
-    if ig is not None and ig[0]:
-        # the same algorithmic work over the average duration rocprofv3 saw for this kernel INSIDE the replayed graph
-        per_s = roofline["work_per_launch"] / (ig[0] * 1e-9)
-        roofline.update(frac_in_graph=round(per_s / (top["peak"] * scale), 4), in_graph_avg_us=round(ig[0] * 1e-3, 2),
-                        in_graph_source=ig[2], profile_top_kernel=ig[3])
-    for r in per_kernel:
-        r.pop("peak", None)
-    roofline["per_kernel"] = per_kernel[:32]
     out = {"metric": "upstream clips/sec (1s@16kHz, 64-mel)", "value": round(B * world * args.steps / dt, 1), "unit": "clips/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if args.precision.startswith("bf16") else "f32",
@@ -533,7 +606,7 @@ def main():
            "config": {"workload": "delores-m upstream step (log-mel + 2 views + q/k conv encoders + MoCo + 3 Barlow heads + bwd + SGD), "
                                   f"1 s @ 16 kHz, 64 mel, batch {B}/GPU, queue {args.queue}", "global_batch": B * world,
                       "parallelism": f"dp{world}"},
-           "final_loss": final_loss, "roofline": roofline}
+           "final_loss": final_loss, "roofline": None, "cpu_baseline": None}
     if gstep is not None:
         ph = gstep.phases
         out["graph_mode"] = ({"mode": "one hipGraph per collective-free phase", "phases": sorted(ph.graphs), "eager_fallback": ph.broken}
@@ -544,10 +617,10 @@ def main():
         out["collectives"] = rccl
     if args.h2d:
         out["h2d"] = {"bytes_per_step": B * 16000 * 4, "pinned": True, "prefetch_batches": 2}
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_steps, args.queue)
-    else:
-        out["cpu_baseline"] = None
+    if args.full:
+        out["roofline"] = roofline_report(prof, prof_steps, dt / args.steps * 1e3, gstep is not None)
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_steps, args.queue)
     print(json.dumps(out))
 
 

@@ -3,7 +3,7 @@ import csv, re, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 ev = sorted(rows, key=lambda r: int(r["Start_Timestamp"]))
 starts = [i for i, r in enumerate(ev) if "logmel" in r["Kernel_Name"]]
-# bench.py: priming steps, warm-up, the timed graph replays, then FIVE eagerly re-issued steps for the per-kernel events - take a
+# bench.py --full: priming steps, warm-up, the timed graph replays, then FIVE eagerly re-issued steps for the per-kernel events - take a
 # step from the middle of the run (a graph replay), not from its tail
 k = int(sys.argv[2]) if len(sys.argv) > 2 else len(starts) // 2
 a, b = starts[k], starts[k + 1]

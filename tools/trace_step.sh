@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-trace}
 mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/raw -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $O/raw -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 cd $R
 T=$(find $O/raw -name "*kernel_trace.csv" | head -1)
 python tools/timeline.py $T > $O/timeline.txt
