@@ -15,6 +15,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -71,18 +73,6 @@ struct GemmArgs {
     const long long* drop_counter;
 };
 
-// kernel names as rocprofv3 prints them (demangled, except for instantiations on __bf16, which its demangler leaves mangled)
-template <typename T> const char* type_code();
-template <> const char* type_code<bf16>() { return "DF16b"; }
-template <> const char* type_code<float>() { return "f"; }
-static const char* note_name(char (&buf)[96], const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return buf;
-}
-#define TF(b) ((b) ? "true" : "false")
 
 template <typename T> struct Mma;
 template <> struct Mma<bf16> {
@@ -495,100 +485,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_kernel(GemmArgs g) {
     gemm_body<T, TA, TB, BK, MI, NW>(g, smem, g.xcd_remap ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x);
 }
 
-// 256 x 256 output tile, 512 threads = 8 waves (2 x 4), each wave 128 x 64 = 4 x 2 accumulators: per 64-deep k-step the
-// tile needs 1,024 L1->LDS cycles against 2,048 MFMA cycles (the 128 x 128 tile: 512 / 512) and 6 fragment reads per 8
-// MFMAs.  For the 6144-row layers (24 x 8 = 192 tiles: one round on 256 CUs).  bf16 only.
-template <bool TA, bool TB>
-__global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g) {
-    constexpr int BK = 64, T256 = 256;
-    using SA = Stage<bf16, TA, BK, T256, 512>;
-    using SB = Stage<bf16, TB, BK, T256, 512>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    bf16* const ldsA0 = reinterpret_cast<bf16*>(smem);
-    bf16* const ldsB0 = ldsA0 + 2 * SA::LDS_ELEMS;
-    const int tiles_n = (g.N + T256 - 1) / T256;
-    int wg = blockIdx.x;
-    if (g.xcd_remap) wg = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const int bm = (wg / tiles_n) * T256, bn = (wg % tiles_n) * T256;
-    const int ksteps = (g.K + BK - 1) / BK;
-    const int per = (ksteps + g.ksplit - 1) / g.ksplit;
-    const int ks0 = blockIdx.z * per, ks1 = min(ksteps, ks0 + per);
-    if (ks0 >= ks1) return;
-    const int kend = min(g.K, ks1 * BK);
-    const __amdgpu_buffer_rsrc_t A = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.A), 0, g.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t B = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.B), 0, g.b_bytes, 0x00020000);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = (wave >> 2) * 128, wn = (wave & 3) * 64;
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    SA sa; SB sb;
-    sa.load(A, g.lda, bm, g.M, ks0 * BK, kend);
-    sb.load(B, g.ldb, bn, g.N, ks0 * BK, kend);
-    sa.put(ldsA0); sb.put(ldsB0);
-    __syncthreads();
-    int cur = 0;
-    for (int ks = ks0; ks < ks1; ++ks) {
-        const bool more = ks + 1 < ks1;
-        if (more) {
-            sa.load(A, g.lda, bm, g.M, (ks + 1) * BK, kend);
-            sb.load(B, g.ldb, bn, g.N, (ks + 1) * BK, kend);
-        }
-        const bf16* la = ldsA0 + cur * SA::LDS_ELEMS;
-        const bf16* lb = ldsB0 + cur * SB::LDS_ELEMS;
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 16) {
-            Vec8<bf16> fa[4], fb[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[i] = SA::frag(la, wm + i * 32, kk, lane);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[j] = SB::frag(lb, wn + j * 32, kk, lane);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) Mma<bf16>::run(acc[i][j], fa[i], fb[j]);
-        }
-        if (more) { sa.put(ldsA0 + (cur ^ 1) * SA::LDS_ELEMS); sb.put(ldsB0 + (cur ^ 1) * SB::LDS_ELEMS); }
-        __syncthreads();
-        cur ^= 1;
-    }
-    // the wave-private epilogue tile holds 64 rows: two passes over the wave's 128
-    epilogue<bf16, 2>(g, *reinterpret_cast<f32x16 (*)[2][2]>(&acc[0]), smem, bm + wm, bn + wn, lane, wave);
-    epilogue<bf16, 2>(g, *reinterpret_cast<f32x16 (*)[2][2]>(&acc[2]), smem, bm + wm + 64, bn + wn, lane, wave);
-}
-
-template <bool TA, bool TB>
-int launch256(const GemmArgs& g, hipStream_t s) {
-    constexpr size_t stage = sizeof(bf16) * 2 * (Stage<bf16, TA, 64, 256, 512>::LDS_ELEMS + Stage<bf16, TB, 64, 256, 512>::LDS_ELEMS);
-    constexpr size_t epi = EPI_LDS * 2;
-    constexpr size_t lds = stage > epi ? stage : epi;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<TA, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, 256) * ceil_div(g.N, 256);
-    GemmArgs ga = g;
-    ga.xcd_remap = tiles % 8 == 0 && tiles >= 64;
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm256_kernel<%s, %s>", TF(TA), TF(TB)); }
-    hipLaunchKernelGGL((gemm256_kernel<TA, TB>), dim3(tiles, 1, g.ksplit), dim3(512), lds, s, ga);
-    ASSL_LAUNCH_CHECK();
-}
-
-int dispatch256(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch256<false, false>(g, s);
-    if (!ta && tb) return launch256<false, true>(g, s);
-    if (ta && tb) return launch256<true, true>(g, s);
-    return launch256<true, false>(g, s);
-}
-
 // Several independent problems of one kind in ONE launch (blockIdx.y = problem): the three Barlow heads of delores_m run
 // the same chain of GEMMs on different operands; issued as separate launches on separate streams they were serialised by
 // the hardware-queue mapping of the graph executor (1.6 ms of a 3.3 ms step), and each launch filled half the chip at best.
@@ -636,39 +532,6 @@ constexpr size_t gemm_lds() {
     return stage > epi ? stage : epi;
 }
 
-template <typename T, bool TA, bool TB, int BK, int MI, int NW = 4>
-int launch_multi(const GemmMulti& gm_, int count, int ksplit, hipStream_t s) {
-    GemmMulti gm = gm_;
-    const int grid = multi_grid(gm, count, 16 * MI * NW, BN);
-    const size_t lds = gemm_lds<T, TA, TB, BK, MI, NW>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_multi_kernel<T, TA, TB, BK, MI, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_multi_kernelI%sLb%dELb%dELi%dELi%dELi%dE", type_code<T>(), (int)TA, (int)TB, BK, MI, NW); }
-    hipLaunchKernelGGL((gemm_multi_kernel<T, TA, TB, BK, MI, NW>), dim3(grid, 1, ksplit), dim3(64 * NW), lds, s, gm);
-    ASSL_LAUNCH_CHECK();
-}
-
-template <typename T, bool TA, bool TB, int BK, int MI, int NW = 4>
-int launch(const GemmArgs& g, hipStream_t s) {
-    const size_t lds = gemm_lds<T, TA, TB, BK, MI, NW>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, TA, TB, BK, MI, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, 16 * MI * NW) * ceil_div(g.N, BN);
-    static const bool remap = getenv("AUDIOSSL_GEMM_XCD") ? atoi(getenv("AUDIOSSL_GEMM_XCD")) != 0 : true;
-    GemmArgs ga = g;
-    ga.xcd_remap = remap && tiles % 8 == 0 && tiles >= 64;
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_kernelI%sLb%dELb%dELi%dELi%dELi%dE", type_code<T>(), (int)TA, (int)TB, BK, MI, NW); }
-    hipLaunchKernelGGL((gemm_kernel<T, TA, TB, BK, MI, NW>), dim3(tiles, 1, g.ksplit), dim3(64 * NW), lds, s, ga);
-    ASSL_LAUNCH_CHECK();
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // bf16 with direct-to-LDS staging (`global_load_lds_dwordx4`) and an NST-deep ring: the pipelined variant.  The
@@ -833,29 +696,6 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs g) {
     epilogue<bf16, MI>(g, acc, smem, bm + wm, bn + wn, lane, wave);
 }
 
-template <bool TA, bool TB, int MI, int NST>
-int launch_ring(const GemmArgs& g, hipStream_t s) {
-    constexpr size_t stage = RingOp<TA, 64 * MI>::BYTES + RingOp<TB, 128>::BYTES;
-    const size_t lds = max((size_t)NST * stage, EPI_LDS);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring_kernel<TA, TB, MI, NST>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, 64 * MI) * ceil_div(g.N, BN);
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_ring_kernel<%s, %s, %d, %d>", TF(TA), TF(TB), MI, NST); }
-    hipLaunchKernelGGL((gemm_ring_kernel<TA, TB, MI, NST>), dim3(tiles, 1, g.ksplit), dim3(256), lds, s, g);
-    ASSL_LAUNCH_CHECK();
-}
-
-template <int MI, int NST>
-int dispatch_ring(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_ring<false, false, MI, NST>(g, s);
-    if (!ta && tb) return launch_ring<false, true, MI, NST>(g, s);
-    if (ta && tb) return launch_ring<true, true, MI, NST>(g, s);
-    return launch_ring<true, false, MI, NST>(g, s);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 256 x 256 output tile, 8 waves (2 x 4, wave tile 128 x 64), K-tile 64, eight phases per pair of K-tiles: the
@@ -1102,20 +942,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs g) {
     p8_body<TA, TB, DBG>(g, smem, xcd_contiguous(blockIdx.x, gridDim.x));
 }
 
-template <bool TA, bool TB, int DBG = 0>
-int launch_p8(const GemmArgs& g, hipStream_t s) {
-    const size_t lds = max((size_t)2 * P8_BUF, EPI_LDS * 2);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_kernel<TA, TB, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, 256) * ceil_div(g.N, 256);
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_p8_kernel<%s, %s, %d>", TF(TA), TF(TB), DBG); }
-    hipLaunchKernelGGL((gemm_p8_kernel<TA, TB, DBG>), dim3(tiles, 1, g.ksplit), dim3(512), lds, s, g);
-    ASSL_LAUNCH_CHECK();
-}
 template <bool TA, bool TB>
 __global__ __launch_bounds__(512) void gemm_p8_multi_kernel(GemmMulti gm) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -1133,56 +959,6 @@ __global__ __launch_bounds__(512) void gemm_p8_multi_sgd_kernel(GemmMulti gm) {
     const int p = multi_locate(gm, wg);
     if (p < 0) return;
     p8_body<TA, TB, 0>(gm.p[p], smem, wg);
-}
-template <bool TA, bool TB>
-int launch_p8_multi(const GemmMulti& gm_, int count, int ksplit, hipStream_t s) {
-    GemmMulti gm = gm_;
-    const int grid = multi_grid(gm, count, 256, 256);
-    const size_t lds = max((size_t)2 * P8_BUF, EPI_LDS * 2);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_multi_kernel<TA, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_multi_sgd_kernel<TA, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    if (gm.p[0].sgd_p) {
-        { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_p8_multi_sgd_kernel<%s, %s>", TF(TA), TF(TB)); }
-        hipLaunchKernelGGL((gemm_p8_multi_sgd_kernel<TA, TB>), dim3(grid, 1, ksplit), dim3(512), lds, s, gm);
-        ASSL_LAUNCH_CHECK();
-    }
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_p8_multi_kernel<%s, %s>", TF(TA), TF(TB)); }
-    hipLaunchKernelGGL((gemm_p8_multi_kernel<TA, TB>), dim3(grid, 1, ksplit), dim3(512), lds, s, gm);
-    ASSL_LAUNCH_CHECK();
-}
-int dispatch_p8_multi(const GemmMulti& gm, int count, int ksplit, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_p8_multi<false, false>(gm, count, ksplit, s);
-    if (!ta && tb) return launch_p8_multi<false, true>(gm, count, ksplit, s);
-    if (ta && tb) return launch_p8_multi<true, true>(gm, count, ksplit, s);
-    return launch_p8_multi<true, false>(gm, count, ksplit, s);
-}
-
-int dispatch_p8(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-#ifdef AUDIOSSL_ABLATE
-    static const int dbg = getenv("AUDIOSSL_GEMM_P8_DBG") ? atoi(getenv("AUDIOSSL_GEMM_P8_DBG")) : 0;   // ablation (wrong results)
-#else
-    constexpr int dbg = 0;            // the ablation instantiations exist only in -DAUDIOSSL_ABLATE builds (python audio-ssl_amd/build.py --ablate)
-#endif
-    if (!ta && !tb && dbg) {
-        switch (dbg) {
-            case 1: return launch_p8<false, false, 1>(g, s);      // no MFMA
-            case 2: return launch_p8<false, false, 2>(g, s);      // no DMA after the first two K-tiles
-            case 4: return launch_p8<false, false, 4>(g, s);      // no fragment reads
-            case 6: return launch_p8<false, false, 6>(g, s);      // MFMA + barriers only
-            case 8: return launch_p8<false, false, 8>(g, s);      // no s_setprio
-            default: break;
-        }
-    }
-    if (!ta && !tb) return launch_p8<false, false>(g, s);
-    if (!ta && tb) return launch_p8<false, true>(g, s);
-    if (ta && tb) return launch_p8<true, true>(g, s);
-    return launch_p8<true, false>(g, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1283,52 +1059,6 @@ __global__ __launch_bounds__(512) void gemm_pk_multi_kernel(GemmMulti gm) {
     const int p = multi_locate(gm, wg);
     if (p < 0) return;
     pk_body<TA, TB, KIND>(gm.p[p], smem, wg);
-}
-template <int KIND> constexpr size_t pk_lds() {
-    return (size_t)P5_NBUF * P5_BUF;
-}
-template <int KIND> constexpr int pk_rows() { return 128; }
-
-template <bool TA, bool TB, int KIND>
-int launch_pk(const GemmArgs& g, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pk_kernel<TA, TB, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pk_lds<KIND>()) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, pk_rows<KIND>()) * ceil_div(g.N, 128);
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_pk_kernel<%s, %s, %d>", TF(TA), TF(TB), KIND); }
-    hipLaunchKernelGGL((gemm_pk_kernel<TA, TB, KIND>), dim3(tiles, 1, g.ksplit), dim3(512), pk_lds<KIND>(), s, g);
-    ASSL_LAUNCH_CHECK();
-}
-template <bool TA, bool TB, int KIND>
-int launch_pk_multi(const GemmMulti& gm_, int count, int ksplit, hipStream_t s) {
-    GemmMulti gm = gm_;
-    const int grid = multi_grid(gm, count, pk_rows<KIND>(), 128);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pk_multi_kernel<TA, TB, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pk_lds<KIND>()) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_pk_multi_kernel<%s, %s, %d>", TF(TA), TF(TB), KIND); }
-    hipLaunchKernelGGL((gemm_pk_multi_kernel<TA, TB, KIND>), dim3(grid, 1, ksplit), dim3(512), pk_lds<KIND>(), s, gm);
-    ASSL_LAUNCH_CHECK();
-}
-template <int KIND>
-int dispatch_pk(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_pk<false, false, KIND>(g, s);
-    if (!ta && tb) return launch_pk<false, true, KIND>(g, s);
-    if (ta && tb) return launch_pk<true, true, KIND>(g, s);
-    return launch_pk<true, false, KIND>(g, s);
-}
-template <int KIND>
-int dispatch_pk_multi(const GemmMulti& gm, int count, int ksplit, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_pk_multi<false, false, KIND>(gm, count, ksplit, s);
-    if (!ta && tb) return launch_pk_multi<false, true, KIND>(gm, count, ksplit, s);
-    if (ta && tb) return launch_pk_multi<true, true, KIND>(gm, count, ksplit, s);
-    return launch_pk_multi<true, false, KIND>(gm, count, ksplit, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1556,20 +1286,6 @@ __global__ __launch_bounds__(512) void gemm_sp_multi_kernel(GemmMulti gm) {
     SpBody<TA, TB, SHAPE>::run(gm.p[p], smem, wg);
 }
 template <bool TA, bool TB, int SHAPE>
-int launch_sp(const GemmArgs& g, hipStream_t s) {
-    using D = SpDim<SHAPE>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_sp_kernel<TA, TB, SHAPE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)D::LDS) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, D::RA) * ceil_div(g.N, D::RB);
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_sp_kernel<%s, %s, %d>", TF(TA), TF(TB), SHAPE); }
-    hipLaunchKernelGGL((gemm_sp_kernel<TA, TB, SHAPE>), dim3(tiles, 1, g.ksplit), dim3(512), D::LDS, s, g);
-    ASSL_LAUNCH_CHECK();
-}
-template <bool TA, bool TB, int SHAPE>
 __global__ __launch_bounds__(512) void gemm_sp_multi_sgd_kernel(GemmMulti gm) {      // see gemm_p8_multi_sgd_kernel
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     int wg;
@@ -1577,43 +1293,7 @@ __global__ __launch_bounds__(512) void gemm_sp_multi_sgd_kernel(GemmMulti gm) { 
     if (p < 0) return;
     SpBody<TA, TB, SHAPE>::run(gm.p[p], smem, wg);
 }
-template <bool TA, bool TB, int SHAPE>
-int launch_sp_multi(const GemmMulti& gm_, int count, int ksplit, hipStream_t s) {
-    using D = SpDim<SHAPE>;
-    GemmMulti gm = gm_;
-    const int grid = multi_grid(gm, count, D::RA, D::RB);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_sp_multi_kernel<TA, TB, SHAPE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)D::LDS) != hipSuccess) return ASSL_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_sp_multi_sgd_kernel<TA, TB, SHAPE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)D::LDS) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    if (gm.p[0].sgd_p) {
-        { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_sp_multi_sgd_kernel<%s, %s, %d>", TF(TA), TF(TB), SHAPE); }
-        hipLaunchKernelGGL((gemm_sp_multi_sgd_kernel<TA, TB, SHAPE>), dim3(grid, 1, ksplit), dim3(512), D::LDS, s, gm);
-        ASSL_LAUNCH_CHECK();
-    }
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_sp_multi_kernel<%s, %s, %d>", TF(TA), TF(TB), SHAPE); }
-    hipLaunchKernelGGL((gemm_sp_multi_kernel<TA, TB, SHAPE>), dim3(grid, 1, ksplit), dim3(512), D::LDS, s, gm);
-    ASSL_LAUNCH_CHECK();
-}
-template <int SHAPE>
-int dispatch_sp(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_sp<false, false, SHAPE>(g, s);
-    if (!ta && tb) return launch_sp<false, true, SHAPE>(g, s);
-    if (ta && tb) return launch_sp<true, true, SHAPE>(g, s);
-    return launch_sp<true, false, SHAPE>(g, s);
-}
-template <int SHAPE>
-int dispatch_sp_multi(const GemmMulti& gm, int count, int ksplit, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_sp_multi<false, false, SHAPE>(gm, count, ksplit, s);
-    if (!ta && tb) return launch_sp_multi<false, true, SHAPE>(gm, count, ksplit, s);
-    if (ta && tb) return launch_sp_multi<true, true, SHAPE>(gm, count, ksplit, s);
-    return launch_sp_multi<true, false, SHAPE>(gm, count, ksplit, s);
-}
-// Shape 6 always runs in this form.  AUDIOSSL_GEMM_SP: bit mask that ALSO moves the 256 x 256 (bit 8) / 128 x 128 (bit 2) tiles to it.
+// Shape 6 always runs in this form; the 256 x 256 and 128 x 128 tiles have it as the non-default variants sp8 / sp5.
 // Measured (tools/heads_gemm_bench.py, tools/gemm_shapes.py; us, sectioned -> pipelined):
 //   256 x 128: three-head M = 1,024 launches NT 35.1 -> 31.3 (822 TF/s), first layer 33.4 -> 30.0, NN 36.5 -> 35.3; single TN
 //              2048 x 2048 x 1024 26.2 -> 23.6, x 512 19.4 -> 17.7                                              -> default
@@ -1623,54 +1303,397 @@ int dispatch_sp_multi(const GemmMulti& gm, int count, int ksplit, int ta, int tb
 //   128 x 128: M = 512 launches 21.9 -> 22.6, 23.3 -> 24.2, 20.4 -> 21.4: two MFMAs per step leave one gap for three reads and a DMA
 //              instruction - the sectioned kernel stays
 //   BK 32 stages for the 256 x 128 / 128 x 128 tiles (rings of 6 / 10): 38.3 vs 31.5 and 25.4 vs 22.5 - twice the barriers
-int sp_mask() {
-    static const int m = getenv("AUDIOSSL_GEMM_SP") ? atoi(getenv("AUDIOSSL_GEMM_SP")) : 0;
-    return m;
-}
 
 // BK = 32 with a register budget for THREE workgroups per CU (41 KB of LDS each; the epilogue runs on half-height tiles so
-// that it fits the same 41 KB); AUDIOSSL_GEMM_BK32=0 disables, =2 also uses it for transposed-A problems.
+// that it fits the same 41 KB).
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256, 3) void gemm_bk32_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     gemm_body<bf16, TA, TB, 32, 2, 4, true>(g, smem, g.xcd_remap ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x);
 }
-template <bool TA, bool TB>
-int launch_bk32(const GemmArgs& g, hipStream_t s) {
-    constexpr size_t stage = sizeof(bf16) * 2 * (Stage<bf16, TA, 32, 128, 256>::LDS_ELEMS + Stage<bf16, TB, 32, BN, 256>::LDS_ELEMS);
-    const size_t lds = stage > EPI_LDS / 2 ? stage : EPI_LDS / 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bk32_kernel<TA, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) return ASSL_ELAUNCH;
-        attr_set = true;
-    }
-    const int tiles = ceil_div(g.M, 128) * ceil_div(g.N, BN);
-    GemmArgs ga = g;
-    ga.xcd_remap = tiles % 8 == 0 && tiles >= 64;
-    { static char nm[96]; g_assl_last_kernel = note_name(nm, "gemm_bk32_kernel<%s, %s>", TF(TA), TF(TB)); }
-    hipLaunchKernelGGL((gemm_bk32_kernel<TA, TB>), dim3(tiles, 1, g.ksplit), dim3(256), lds, s, ga);
-    ASSL_LAUNCH_CHECK();
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernel set: these instantiations and no others are compiled into the library (a -DAUDIOSSL_ABLATE build adds the ablation variants
+// of gemm_p8_kernel, see launch_variant).  Keep the order.  It is the order in which the kernels have been emitted since they were
+// written, and the machine code the compiler produces for a kernel is not independent of what the module holds before it (emitting the
+// single-problem kernels first changed the register allocation of two multi-problem ones): with the order pinned, a change to the host
+// side below leaves every kernel byte for byte as it was.
+#define FOR_LAYOUTS(X, ...) X(false, false, __VA_ARGS__) X(false, true, __VA_ARGS__) X(true, true, __VA_ARGS__) X(true, false, __VA_ARGS__)
+#define KERNEL(TA, TB, NAME, ARGS, ...) template __global__ void NAME<TA, TB, ##__VA_ARGS__>(ARGS);
+#define KERNEL_AND_SGD(TA, TB, STEM, ...) KERNEL(TA, TB, STEM##_kernel, GemmMulti, ##__VA_ARGS__) KERNEL(TA, TB, STEM##_sgd_kernel, GemmMulti, ##__VA_ARGS__)
+#define REG_KERNEL(TA, TB, NAME, ARGS, T, BK, MI) template __global__ void NAME<T, TA, TB, BK, MI, 4>(ARGS);
+FOR_LAYOUTS(KERNEL_AND_SGD, gemm_p8_multi)
+FOR_LAYOUTS(KERNEL, gemm_p8_kernel, GemmArgs, 0)
+FOR_LAYOUTS(KERNEL, gemm_bk32_kernel, GemmArgs)
+FOR_LAYOUTS(KERNEL_AND_SGD, gemm_sp_multi, 6)
+FOR_LAYOUTS(KERNEL_AND_SGD, gemm_sp_multi, 5)
+FOR_LAYOUTS(KERNEL, gemm_pk_multi_kernel, GemmMulti, 5)
+FOR_LAYOUTS(KERNEL_AND_SGD, gemm_sp_multi, 8)
+FOR_LAYOUTS(REG_KERNEL, gemm_multi_kernel, GemmMulti, bf16, 64, 1)
+FOR_LAYOUTS(REG_KERNEL, gemm_multi_kernel, GemmMulti, bf16, 128, 2)
+FOR_LAYOUTS(REG_KERNEL, gemm_multi_kernel, GemmMulti, bf16, 64, 2)
+FOR_LAYOUTS(KERNEL, gemm_sp_kernel, GemmArgs, 6)
+FOR_LAYOUTS(KERNEL, gemm_sp_kernel, GemmArgs, 8)
+FOR_LAYOUTS(KERNEL, gemm_sp_kernel, GemmArgs, 5)
+FOR_LAYOUTS(KERNEL, gemm_pk_kernel, GemmArgs, 5)
+FOR_LAYOUTS(KERNEL, gemm_ring_kernel, GemmArgs, 1, 4)
+FOR_LAYOUTS(KERNEL, gemm_ring_kernel, GemmArgs, 2, 4)
+FOR_LAYOUTS(REG_KERNEL, gemm_kernel, GemmArgs, bf16, 64, 1)
+FOR_LAYOUTS(REG_KERNEL, gemm_kernel, GemmArgs, bf16, 128, 2)
+FOR_LAYOUTS(REG_KERNEL, gemm_kernel, GemmArgs, bf16, 64, 2)
+FOR_LAYOUTS(REG_KERNEL, gemm_kernel, GemmArgs, float, 32, 2)
+#undef FOR_LAYOUTS
+#undef KERNEL
+#undef KERNEL_AND_SGD
+#undef REG_KERNEL
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side.  A VARIANT is one kernel family at one tile shape.  Every entry point runs
+//   validate the operands -> describe the problem -> choose a variant (pure functions) -> one switch that launches it.
+enum Variant { V_NONE = -1, V_REG64, V_REG128_K64, V_REG128_K128, V_RING64, V_RING128, V_BK32, V_P8, V_PK5, V_SP5, V_SP6, V_SP8, V_COUNT };
+// the names DESIGN.md section 4 uses; AUDIOSSL_GEMM_FORCE / AUDIOSSL_GEMM_OFF take them
+const char* const VARIANT_NAME[V_COUNT] = {"reg64x128", "reg128_k64", "reg128_k128", "ring64", "ring128", "bk32", "p8", "pk5", "sp5", "sp6", "sp8"};
+
+// What the choice looks at: one problem (multi = false), or `count` problems with common M, transposes and epilogue in one launch.
+struct Problem {
+    bool multi;
+    int count, ta, tb, M, ksplit, atomic, lse_mode;
+    const int* Nv; const int* K;                             // one entry per problem
+    int N, kmin;                                             // widest problem, shortest contraction
+};
+Problem describe(bool multi, int count, int ta, int tb, int M, const int* Nv, const int* K, int ksplit, int atomic, int lse_mode) {
+    Problem p{multi, count, ta, tb, M, ksplit, atomic, lse_mode, Nv, K, 0, 1 << 30};
+    for (int i = 0; i < count; ++i) { p.N = max(p.N, Nv[i]); p.kmin = min(p.kmin, K[i]); }
+    return p;
 }
-int dispatch_bk32(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch_bk32<false, false>(g, s);
-    if (!ta && tb) return launch_bk32<false, true>(g, s);
-    if (ta && tb) return launch_bk32<true, true>(g, s);
-    return launch_bk32<true, false>(g, s);
+// tiles of 128 x 128 / 256 x 128 / 256 x 256 over all problems and K splits; blocks: the register-staged grid of 128 x 128 tiles, which is
+// sized for the widest problem
+struct Tiles { long t5, t6, t8, blocks; };
+Tiles count_tiles(const Problem& p) {
+    Tiles t{0, 0, 0, (long)ceil_div(p.M, BM) * ceil_div(p.N, BN) * p.ksplit * p.count};
+    for (int i = 0; i < p.count; ++i) {
+        t.t5 += (long)ceil_div(p.M, 128) * ceil_div(p.Nv[i], 128);
+        t.t6 += (long)ceil_div(p.M, 256) * ceil_div(p.Nv[i], 128);
+        t.t8 += (long)ceil_div(p.M, 256) * ceil_div(p.Nv[i], 256);
+    }
+    t.t5 *= p.ksplit; t.t6 *= p.ksplit; t.t8 *= p.ksplit;
+    return t;
 }
 
-template <typename T, int BK, int MI, int NW = 4>
-int dispatch(const GemmArgs& g, int ta, int tb, hipStream_t s) {
-    if (!ta && !tb) return launch<T, false, false, BK, MI, NW>(g, s);
-    if (!ta && tb) return launch<T, false, true, BK, MI, NW>(g, s);
-    if (ta && tb) return launch<T, true, true, BK, MI, NW>(g, s);
-    return launch<T, true, false, BK, MI, NW>(g, s);
+// Where a variant may run at all, bf16 operands (the choice functions add where it is measured to win; AUDIOSSL_GEMM_FORCE needs only this).
+bool legal(Variant v, const Problem& p, const Tiles& t) {
+    // the hand-scheduled kernels: K % 64, whole 16-byte rows, at least one full tile of the smallest shape
+    bool hs_ok = p.M >= 128 && p.N >= 128 && (!p.ta || p.M % 8 == 0);
+    for (int i = 0; i < p.count; ++i) hs_ok = hs_ok && p.K[i] % GBK == 0 && (!p.tb || p.Nv[i] % 8 == 0);
+    switch (v) {
+        case V_REG64:       return t.blocks <= 128 && p.M > 64;
+        case V_REG128_K64:  return true;
+        case V_REG128_K128: return t.blocks <= 256 && p.kmin >= 512;
+        case V_RING64:
+        case V_RING128:     return !p.multi && p.kmin % GBK == 0 && p.M >= 8 && p.N >= 8;      // no multi-problem kernel
+        case V_BK32:        return !p.multi && t.blocks >= 512;                                // no multi-problem kernel
+        case V_P8:
+        case V_SP8:         return hs_ok && p.M >= 256 && p.N >= 256;
+        case V_SP6:         return hs_ok && !p.lse_mode && p.M >= 256;
+        case V_PK5:
+        case V_SP5:         return hs_ok && !p.lse_mode;
+        default:            return false;
+    }
+}
+
+struct Choice { Variant v; int ksplit; };                    // ksplit: the caller's, or raised (256 x 256 tiles with an accumulating output)
+
+// the 256 x 256 kernels on accumulating outputs: split K until the chip is full
+int p8_ksplit(const Problem& p, const Tiles& t) {
+    const long t256 = t.t8 / p.ksplit;
+    int ks = p.ksplit;
+    if (!p.multi && p.atomic == 1 && t256 * ks < 192)
+        while (t256 * ks * 2 <= 256 && p.kmin / (ks * 2) >= 1024) ks *= 2;
+    return ks;
+}
+
+// kernel choice for one bf16 problem (measured rules, see the comments inside); off: bit v set = skip variant v
+Choice choose_single(const Problem& p, const Tiles& t, unsigned off) {
+    const int M = p.M, K = p.kmin, ksplit = p.ksplit;
+    const auto on = [&](Variant v) { return !(off >> v & 1) && legal(v, p, t); };
+    // transposed-A problems whose split-K launch fills the chip with 256 x 128 tiles: the software-pipelined kernel with the caller's
+    // split beats the 256 x 256 kernel with the split raised to fill the chip (the encoder's fc.3 weight gradient, 2048 x 2048 x 6144
+    // split in two: 97.4 -> 77.6 us, 664 TFLOP/s)
+    if (on(V_SP6) && p.ta && p.atomic == 1 && t.t6 >= 192 && t.t6 <= 288 && K / ksplit >= 2048) return {V_SP6, ksplit};
+    if (on(V_P8)) {
+        // measured (tools/gemm_shapes.py, gemm_one.py): it wins once the 256 x 256 tiles occupy at least half of the CUs and every
+        // workgroup walks >= 16 K-tiles (6144 x 2048 x 2048 NT 83.9 -> 63.0 us with the bias / ReLU / dropout epilogue, NN 71.0 ->
+        // 60.4; 4096^3 214 -> 127 us, 8192^3 1.30 PFLOP/s); with few K-tiles its one-workgroup-per-CU epilogue is exposed
+        // (6144 x 2048 x 512: 30.8 vs 27.2 us) and on small grids the 128-row kernels spread over more CUs.
+        const long t256 = t.t8 / ksplit;
+        const int ks = p8_ksplit(p, t);
+        // ... and with 12 K-tiles once the grid is several rounds deep (the transformer blocks' K = 768 layers at 27,648 rows:
+        // 27648 x 2304 x 768 NT 188.6 -> 140.5 us, x 3072 235.3 -> 181.2, x 768 63.9 -> 53.2 against the K-step-32 kernel)
+        const bool deep = t256 * ks >= 512 && K / ks >= 768;
+        if (t256 * ks >= 128 && (K / ks >= 1024 || deep)) return {V_P8, ks};
+    }
+    // the 256 x 128 kernel (written for the multi-problem launches of the projector heads, see choose_multi):
+    // single problems whose 256 x 128 tiles fill the chip once while the 256 x 256 tiles would leave half of it idle
+    if (on(V_SP6) && t.t6 >= 128 && t.t6 <= 288 && t.t8 < 128 && K / ksplit >= 512) return {V_SP6, ksplit};
+    // measured (tools/gemm_shapes.py): NN 6144 x 512 x 2048 34.1 -> 25.8 us, TN 2048 x 512 x 6144 / 3 41.9 -> 32.2 us; with short K
+    // loops (2048 x 2048 x 512 TN: 19.3 vs 17.9 us) and for K-contiguous operands on <= 128 tiles (the ring kernel: 20.2 vs 21.7 us)
+    // the older kernels stay
+    if (on(V_PK5) && t.t5 >= 96 && t.t5 <= 288 && t.t6 < 128 && K / ksplit >= 1024 && (p.ta || p.tb || t.t5 > 128)) return {V_PK5, ksplit};
+    // grids of >= 2 workgroups per CU with a K-contiguous A operand: K-step 32 and THREE co-resident workgroups per CU (41 KB
+    // of LDS each, 126 VGPRs) - 12 waves per CU hide the staged-load and barrier waits better than two workgroups at K-step
+    // 64 (6144x2048x2048 NT 80.9 -> 71.5 us, NN 90.2 -> 76.8 us; with a transposed A operand it measured slower)
+    if (on(V_BK32) && !p.ta) return {V_BK32, ksplit};
+    // measured (tools/gemm_shapes.py): the ring wins for K-contiguous operands (NT) on grids of at most two waves of
+    // workgroups - 64-row tiles up to 128 full tiles, 128-row tiles up to 512; with a transposed operand or on larger grids
+    // two co-resident workgroups of the register-staged kernel overlap each other better
+    if (on(V_RING64) && !p.ta && !p.tb && t.blocks <= 128 && M > 64) return {V_RING64, ksplit};
+    if (on(V_RING128) && !p.ta && !p.tb && t.blocks > 128 && t.blocks <= 512) return {V_RING128, ksplit};
+    // these shapes are latency-bound per workgroup (~0.5 us per 64-deep k-step whatever the tile): when 128 x 128 tiles
+    // would occupy at most half of the 256 CUs, halve the tile in M and run twice as many workgroups
+    if (on(V_REG64)) return {V_REG64, ksplit};
+    return {on(V_REG128_K128) ? V_REG128_K128 : V_REG128_K64, ksplit};
+}
+
+// kernel choice for a multi-problem launch
+Choice choose_multi(const Problem& p, const Tiles& t, unsigned off) {
+    const int ksplit = p.ksplit;
+    const auto on = [&](Variant v) { return !(off >> v & 1) && legal(v, p, t); };
+    // the 256 x 128 kernel: problems whose 256 x 256 tiles would leave more than half of the CUs idle while the 256 x 128 tiles
+    // fit the chip in one round (the M = 1,024 layers and data gradients of the three heads: 192 workgroups); the 128 x 128 kernel
+    // where even those are too few (M = 512: 96 -> 192 workgroups)
+    if (on(V_SP6) && t.t6 >= 128 && t.t6 <= 288 && t.t8 < 128 && p.kmin >= 512) return {V_SP6, ksplit};
+    if (on(V_PK5) && t.t5 >= 96 && t.t5 <= 288 && t.t6 < 128 && p.kmin >= 512) return {V_PK5, ksplit};
+    // multi-problem launches: measured wins for the transposed-A weight gradients of the three heads (2048 x 2048 x 1024:
+    // 50.9 -> 43.9 us, x 512: 31.3 -> 29.0 us)
+    if (on(V_P8) && p.ta && t.t8 >= 128 && p.kmin >= 512) return {V_P8, ksplit};
+    if (on(V_REG64)) return {V_REG64, ksplit};
+    return {on(V_REG128_K128) ? V_REG128_K128 : V_REG128_K64, ksplit};
+}
+
+// The two diagnostic switches, read once per process (tests force variants in a child process):
+//   AUDIOSSL_GEMM_FORCE=<variant>            every bf16 problem for which the variant is legal runs it; the rest take the default choice
+//   AUDIOSSL_GEMM_OFF=<variant>[,<variant>]  the default choice skips these (reg128_k64 is the last resort and cannot be skipped)
+// An unknown name makes every GEMM entry point return ASSL_EINVAL: a misspelt switch must not silently run the default.
+struct Switches { Variant force; unsigned off; bool bad; };
+const Switches& switches() {
+    static const Switches sw = [] {
+        Switches r{V_NONE, 0, false};
+        for (int w = 0; w < 2; ++w) {
+            const bool is_force = w == 0;
+            const char* s = getenv(is_force ? "AUDIOSSL_GEMM_FORCE" : "AUDIOSSL_GEMM_OFF");
+            while (s && *s) {
+                const char* e = strchr(s, ',');
+                const size_t n = e ? (size_t)(e - s) : strlen(s);
+                Variant v = V_NONE;
+                for (int i = 0; i < V_COUNT; ++i)
+                    if (strlen(VARIANT_NAME[i]) == n && !strncmp(VARIANT_NAME[i], s, n)) v = (Variant)i;
+                if (v == V_NONE || (is_force && (e || r.force != V_NONE))) r.bad = true;
+                else if (is_force) r.force = v;
+                else r.off |= 1u << v;
+                s = e ? e + 1 : s + n;
+            }
+        }
+        return r;
+    }();
+    return sw;
+}
+
+Choice choose(const Problem& p) {
+    const Switches& sw = switches();
+    const Tiles t = count_tiles(p);
+    if (sw.force != V_NONE && legal(sw.force, p, t))
+        return {sw.force, sw.force == V_P8 || sw.force == V_SP8 ? p8_ksplit(p, t) : p.ksplit};
+    return p.multi ? choose_multi(p, t, sw.off) : choose_single(p, t, sw.off);
+}
+
+// One kernel instantiation: entry, the name rocprofv3 prints for it (demangled, except for instantiations on __bf16, which its
+// demangler leaves mangled), output tile, workgroup size, dynamic LDS.  Built once, on first use, which is also when the LDS limit
+// of the kernel is raised; immutable afterwards (g_assl_last_kernel only ever points at these names).
+template <typename Args>
+struct Kernel { void (*fn)(Args); char name[96]; int rows, cols, block; size_t lds; hipError_t attr; };
+template <typename Args>
+Kernel<Args> make_kernel(void (*fn)(Args), int rows, int cols, int block, size_t lds, const char* fmt, ...) {
+    Kernel<Args> k{fn, {0}, rows, cols, block, lds, hipSuccess};
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(k.name, sizeof(k.name), fmt, ap);
+    va_end(ap);
+    k.attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return k;
+}
+#define TF(b) ((b) ? "true" : "false")
+template <typename T> const char* type_code();
+template <> const char* type_code<bf16>() { return "DF16b"; }
+template <> const char* type_code<float>() { return "f"; }
+
+// the one launcher
+template <typename Args>
+int launch_kernel(const Kernel<Args>& k, int grid, int ksplit, hipStream_t s, const Args& a) {
+    if (k.attr != hipSuccess) return ASSL_ELAUNCH;
+    g_assl_last_kernel = k.name;
+    void* args[] = {const_cast<Args*>(&a)};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(k.fn), dim3(grid, 1, ksplit), dim3(k.block), args, k.lds, s);
+    ASSL_LAUNCH_CHECK();
+}
+// one problem: a grid of the kernel's tiles.  remap: the kernels that take their XCD-contiguous tile order from g.xcd_remap
+int launch_single(const Kernel<GemmArgs>& k, const GemmArgs& g, bool remap, hipStream_t s) {
+    const int tiles = ceil_div(g.M, k.rows) * ceil_div(g.N, k.cols);
+    GemmArgs ga = g;
+    ga.xcd_remap = remap && tiles % 8 == 0 && tiles >= 64;
+    return launch_kernel(k, tiles, g.ksplit, s, ga);
+}
+int launch_multi(const Kernel<GemmMulti>& k, const GemmMulti& gm_, int count, int ksplit, hipStream_t s) {
+    GemmMulti gm = gm_;
+    return launch_kernel(k, multi_grid(gm, count, k.rows, k.cols), ksplit, s, gm);
+}
+
+// (ta, tb) -> the <TA, TB> instantiation of a templated callable: f(std::bool_constant<TA>, std::bool_constant<TB>)
+template <typename F>
+int by_layout(int ta, int tb, F&& f) {
+    if (!ta && !tb) return f(std::false_type{}, std::false_type{});
+    if (!ta && tb) return f(std::false_type{}, std::true_type{});
+    if (ta && tb) return f(std::true_type{}, std::true_type{});
+    return f(std::true_type{}, std::false_type{});
+}
+
+// The kernel table: per family, what a launch needs beyond the kernel itself - tile shape, workgroup size, LDS bytes, name.
+template <typename T, bool TA, bool TB, int BK, int MI>
+const Kernel<GemmArgs>& reg_kernel() {
+    static const auto k = make_kernel(&gemm_kernel<T, TA, TB, BK, MI, 4>, 64 * MI, BN, 256, gemm_lds<T, TA, TB, BK, MI, 4>(),
+                                      "gemm_kernelI%sLb%dELb%dELi%dELi%dELi%dE", type_code<T>(), (int)TA, (int)TB, BK, MI, 4);
+    return k;
+}
+template <bool TA, bool TB, int BK, int MI>
+const Kernel<GemmMulti>& reg_multi_kernel() {
+    static const auto k = make_kernel(&gemm_multi_kernel<bf16, TA, TB, BK, MI, 4>, 64 * MI, BN, 256, gemm_lds<bf16, TA, TB, BK, MI, 4>(),
+                                      "gemm_multi_kernelI%sLb%dELb%dELi%dELi%dELi%dE", type_code<bf16>(), (int)TA, (int)TB, BK, MI, 4);
+    return k;
+}
+template <bool TA, bool TB, int MI>
+const Kernel<GemmArgs>& ring_kernel() {
+    constexpr int NST = 4;                                   // ring depth (2, 3 and 6 were swept and dropped)
+    constexpr size_t stage = RingOp<TA, 64 * MI>::BYTES + RingOp<TB, 128>::BYTES;
+    static const auto k = make_kernel(&gemm_ring_kernel<TA, TB, MI, NST>, 64 * MI, BN, 256, max((size_t)NST * stage, EPI_LDS),
+                                      "gemm_ring_kernel<%s, %s, %d, %d>", TF(TA), TF(TB), MI, NST);
+    return k;
+}
+template <bool TA, bool TB>
+const Kernel<GemmArgs>& bk32_kernel() {
+    constexpr size_t stage = sizeof(bf16) * 2 * (Stage<bf16, TA, 32, 128, 256>::LDS_ELEMS + Stage<bf16, TB, 32, BN, 256>::LDS_ELEMS);
+    static const auto k = make_kernel(&gemm_bk32_kernel<TA, TB>, 128, BN, 256, stage > EPI_LDS / 2 ? stage : EPI_LDS / 2,
+                                      "gemm_bk32_kernel<%s, %s>", TF(TA), TF(TB));
+    return k;
+}
+constexpr size_t P8_LDS = (size_t)2 * P8_BUF > EPI_LDS * 2 ? (size_t)2 * P8_BUF : EPI_LDS * 2;
+template <bool TA, bool TB, int DBG>
+const Kernel<GemmArgs>& p8_kernel() {
+    static const auto k = make_kernel(&gemm_p8_kernel<TA, TB, DBG>, 256, 256, 512, P8_LDS, "gemm_p8_kernel<%s, %s, %d>", TF(TA), TF(TB), DBG);
+    return k;
+}
+template <bool TA, bool TB>
+const Kernel<GemmMulti>& p8_multi_kernel(bool sgd) {         // sgd: the same kernel under the name it carries when the epilogue applies the update
+    static const auto k = make_kernel(&gemm_p8_multi_kernel<TA, TB>, 256, 256, 512, P8_LDS, "gemm_p8_multi_kernel<%s, %s>", TF(TA), TF(TB));
+    static const auto ks = make_kernel(&gemm_p8_multi_sgd_kernel<TA, TB>, 256, 256, 512, P8_LDS, "gemm_p8_multi_sgd_kernel<%s, %s>", TF(TA), TF(TB));
+    return sgd ? ks : k;
+}
+constexpr size_t PK5_LDS = (size_t)P5_NBUF * P5_BUF;
+template <bool TA, bool TB>
+const Kernel<GemmArgs>& pk5_kernel() {
+    static const auto k = make_kernel(&gemm_pk_kernel<TA, TB, 5>, 128, 128, 512, PK5_LDS, "gemm_pk_kernel<%s, %s, %d>", TF(TA), TF(TB), 5);
+    return k;
+}
+template <bool TA, bool TB>
+const Kernel<GemmMulti>& pk5_multi_kernel() {
+    static const auto k = make_kernel(&gemm_pk_multi_kernel<TA, TB, 5>, 128, 128, 512, PK5_LDS, "gemm_pk_multi_kernel<%s, %s, %d>", TF(TA), TF(TB), 5);
+    return k;
+}
+template <bool TA, bool TB, int SHAPE>
+const Kernel<GemmArgs>& sp_kernel() {
+    using D = SpDim<SHAPE>;
+    static const auto k = make_kernel(&gemm_sp_kernel<TA, TB, SHAPE>, D::RA, D::RB, 512, D::LDS, "gemm_sp_kernel<%s, %s, %d>", TF(TA), TF(TB), SHAPE);
+    return k;
+}
+template <bool TA, bool TB, int SHAPE>
+const Kernel<GemmMulti>& sp_multi_kernel(bool sgd) {
+    using D = SpDim<SHAPE>;
+    static const auto k = make_kernel(&gemm_sp_multi_kernel<TA, TB, SHAPE>, D::RA, D::RB, 512, D::LDS, "gemm_sp_multi_kernel<%s, %s, %d>", TF(TA), TF(TB), SHAPE);
+    static const auto ks = make_kernel(&gemm_sp_multi_sgd_kernel<TA, TB, SHAPE>, D::RA, D::RB, 512, D::LDS, "gemm_sp_multi_sgd_kernel<%s, %s, %d>", TF(TA), TF(TB), SHAPE);
+    return sgd ? ks : k;
+}
+
+int launch_variant(Variant v, const GemmArgs& g, int ta, int tb, hipStream_t s) {
+    return by_layout(ta, tb, [&](auto a, auto b) {
+        constexpr bool TA = decltype(a)::value, TB = decltype(b)::value;
+        switch (v) {
+            case V_REG64:       return launch_single(reg_kernel<bf16, TA, TB, 64, 1>(), g, true, s);
+            case V_REG128_K64:  return launch_single(reg_kernel<bf16, TA, TB, 64, 2>(), g, true, s);
+            case V_REG128_K128: return launch_single(reg_kernel<bf16, TA, TB, 128, 2>(), g, true, s);
+            case V_RING64:      return launch_single(ring_kernel<TA, TB, 1>(), g, false, s);
+            case V_RING128:     return launch_single(ring_kernel<TA, TB, 2>(), g, false, s);
+            case V_BK32:        return launch_single(bk32_kernel<TA, TB>(), g, true, s);
+            case V_P8:
+#ifdef AUDIOSSL_ABLATE
+                // ablation variants of the main loop (WRONG results by design); they exist only in -DAUDIOSSL_ABLATE builds
+                // (python audio-ssl_amd/build.py --ablate)
+                if (!TA && !TB) {
+                    static const char* const e = getenv("AUDIOSSL_GEMM_P8_DBG");
+                    static const int dbg = e ? atoi(e) : 0;
+                    switch (dbg) {
+                        case 1: return launch_single(p8_kernel<false, false, 1>(), g, false, s);      // no MFMA
+                        case 2: return launch_single(p8_kernel<false, false, 2>(), g, false, s);      // no DMA after the first two K-tiles
+                        case 4: return launch_single(p8_kernel<false, false, 4>(), g, false, s);      // no fragment reads
+                        case 6: return launch_single(p8_kernel<false, false, 6>(), g, false, s);      // MFMA + barriers only
+                        case 8: return launch_single(p8_kernel<false, false, 8>(), g, false, s);      // no s_setprio
+                        default: break;
+                    }
+                }
+#endif
+                                return launch_single(p8_kernel<TA, TB, 0>(), g, false, s);
+            case V_PK5:         return launch_single(pk5_kernel<TA, TB>(), g, false, s);
+            case V_SP5:         return launch_single(sp_kernel<TA, TB, 5>(), g, false, s);
+            case V_SP6:         return launch_single(sp_kernel<TA, TB, 6>(), g, false, s);
+            case V_SP8:         return launch_single(sp_kernel<TA, TB, 8>(), g, false, s);
+            default:            return ASSL_EINVAL;
+        }
+    });
+}
+
+int launch_variant_multi(Variant v, const GemmMulti& gm, int count, int ksplit, int ta, int tb, hipStream_t s) {
+    const bool sgd = gm.p[0].sgd_p != nullptr;
+    return by_layout(ta, tb, [&](auto a, auto b) {
+        constexpr bool TA = decltype(a)::value, TB = decltype(b)::value;
+        switch (v) {
+            case V_REG64:       return launch_multi(reg_multi_kernel<TA, TB, 64, 1>(), gm, count, ksplit, s);
+            case V_REG128_K64:  return launch_multi(reg_multi_kernel<TA, TB, 64, 2>(), gm, count, ksplit, s);
+            case V_REG128_K128: return launch_multi(reg_multi_kernel<TA, TB, 128, 2>(), gm, count, ksplit, s);
+            case V_P8:          return launch_multi(p8_multi_kernel<TA, TB>(sgd), gm, count, ksplit, s);
+            case V_PK5:         return launch_multi(pk5_multi_kernel<TA, TB>(), gm, count, ksplit, s);
+            case V_SP5:         return launch_multi(sp_multi_kernel<TA, TB, 5>(sgd), gm, count, ksplit, s);
+            case V_SP6:         return launch_multi(sp_multi_kernel<TA, TB, 6>(sgd), gm, count, ksplit, s);
+            case V_SP8:         return launch_multi(sp_multi_kernel<TA, TB, 8>(sgd), gm, count, ksplit, s);
+            default:            return ASSL_EINVAL;                  // ring, bk32: never legal here
+        }
+    });
+}
+
+// one bf16 problem, validated: choose and launch
+int run_bf16(const GemmArgs& g, int ta, int tb, hipStream_t s) {
+    if (switches().bad) return ASSL_EINVAL;
+    const Choice c = choose(describe(false, 1, ta, tb, g.M, &g.N, &g.K, g.ksplit, g.atomic, g.lse_mode));
+    GemmArgs ga = g;
+    ga.ksplit = c.ksplit;
+    return launch_variant(c.v, ga, ta, tb, s);
+}
+// count bf16 problems, validated (every gm.p[i] describes one): choose and launch
+int run_multi(const GemmMulti& gm, int count, int ta, int tb, const int* Nv, const int* K, hipStream_t s) {
+    if (switches().bad) return ASSL_EINVAL;
+    const Choice c = choose(describe(true, count, ta, tb, gm.p[0].M, Nv, K, gm.p[0].ksplit, gm.p[0].atomic, 0));
+    return launch_variant_multi(c.v, gm, count, c.ksplit, ta, tb, s);
 }
 
 // the 8-columns-per-lane epilogue needs whole, aligned vectors of every operand it touches
 int epi_vectorisable(const GemmArgs& g, int dtype) {
-    static const bool on = getenv("AUDIOSSL_GEMM_VEC_EPI") ? atoi(getenv("AUDIOSSL_GEMM_VEC_EPI")) != 0 : true;
-    if (!on || dtype != 1 || g.atomic == 1 || g.N % 8) return 0;
+    if (dtype != 1 || g.atomic == 1 || g.N % 8) return 0;
     const size_t csz = g.out_f32 ? 4 : 2;
     if (((size_t)g.C * 1) % 16 || (g.ldc * csz) % 16) return 0;
     if (g.bias && (size_t)g.bias % 16) return 0;
@@ -1680,82 +1703,43 @@ int epi_vectorisable(const GemmArgs& g, int dtype) {
     return 1;
 }
 
-}  // namespace
-
-static int dispatch_multi(const GemmMulti& gm, int count, int M, int N, int kmin, int ksplit, int trans_a, int trans_b, hipStream_t s,
-                          const int* K, const int* Nv) {
-    const long blocks = (long)ceil_div(M, BM) * ceil_div(N, BN) * ksplit * count;
-    const bool small = blocks <= 128 && M > 64;
-#define MULTI(BK_, MI_, NW_)                                                                              \
-    do {                                                                                                  \
-        if (!trans_a && !trans_b) return launch_multi<bf16, false, false, BK_, MI_, NW_>(gm, count, ksplit, s); \
-        if (!trans_a && trans_b) return launch_multi<bf16, false, true, BK_, MI_, NW_>(gm, count, ksplit, s);   \
-        if (trans_a && trans_b) return launch_multi<bf16, true, true, BK_, MI_, NW_>(gm, count, ksplit, s);     \
-        return launch_multi<bf16, true, false, BK_, MI_, NW_>(gm, count, ksplit, s);                            \
-    } while (0)
-    static const int p8 = getenv("AUDIOSSL_GEMM_P8") ? atoi(getenv("AUDIOSSL_GEMM_P8")) : -1;
-    static const int p6 = getenv("AUDIOSSL_GEMM_P6") ? atoi(getenv("AUDIOSSL_GEMM_P6")) : -1;
-    bool hs_ok = M >= 128 && N >= 128 && (!trans_a || M % 8 == 0);           // the hand-scheduled kernels: K % 64, whole 16-byte rows
-    long t5 = 0, t6 = 0, t8 = 0;
-    for (int i = 0; i < count; ++i) {
-        hs_ok = hs_ok && K[i] % GBK == 0 && (!trans_b || Nv[i] % 8 == 0);
-        t5 += (long)ceil_div(M, 128) * ceil_div(Nv[i], 128);
-        t6 += (long)ceil_div(M, 256) * ceil_div(Nv[i], 128);
-        t8 += (long)ceil_div(M, 256) * ceil_div(Nv[i], 256);
-    }
-    t5 *= ksplit; t6 *= ksplit; t8 *= ksplit;
-    // the 256 x 128 kernel: problems whose 256 x 256 tiles would leave more than half of the CUs idle while the 256 x 128 tiles
-    // fit the chip in one round (the M = 1,024 layers and data gradients of the three heads: 192 workgroups); the 128 x 128 kernel
-    // where even those are too few (M = 512: 96 -> 192 workgroups)
-    if (p6 != 0 && hs_ok && M >= 256 && (p6 == 1 || (t6 >= 128 && t6 <= 288 && t8 < 128 && kmin >= 512)))
-    {
-        return dispatch_sp_multi<6>(gm, count, ksplit, trans_a, trans_b, s);
-    }
-    if (p6 != 0 && hs_ok && (p6 == 5 || (p6 != 1 && t5 >= 96 && t5 <= 288 && t6 < 128 && kmin >= 512)))
-    {
-        if (sp_mask() & 2) return dispatch_sp_multi<5>(gm, count, ksplit, trans_a, trans_b, s);
-        return dispatch_pk_multi<5>(gm, count, ksplit, trans_a, trans_b, s);
-    }
-    // multi-problem launches: measured wins for the transposed-A weight gradients of the three heads (2048 x 2048 x 1024:
-    // 50.9 -> 43.9 us, x 512: 31.3 -> 29.0 us)
-    if (p8 != 0 && p8 != 2 && hs_ok && M >= 256 && N >= 256 && (p8 == 1 || (trans_a && t8 >= 128 && kmin >= 512)))
-    {
-        if (sp_mask() & 8) return dispatch_sp_multi<8>(gm, count, ksplit, trans_a, trans_b, s);
-        return dispatch_p8_multi(gm, count, ksplit, trans_a, trans_b, s);
-    }
-    static const int w8 = getenv("AUDIOSSL_GEMM_W8") ? atoi(getenv("AUDIOSSL_GEMM_W8")) : 0;
-    if (w8 && M >= 256) MULTI(64, 2, 8);
-    if (small) MULTI(64, 1, 4);
-    if (blocks <= 256 && kmin >= 512) MULTI(128, 2, 4);
-    MULTI(64, 2, 4);
-#undef MULTI
+// The operand rules of every entry point, and the start of its GemmArgs (zero-initialised: no epilogue term, keep_scale 1, one K split):
+// the vector (8-element) dimension of each operand is a multiple of 8 (ASSL_EINVAL), base pointers and rows are 16-byte aligned -
+// the entry point's other pointers too, passed as extra_aligned - (ASSL_EALIGN), and the extents fit 32-bit buffer offsets (ASSL_EINVAL).
+int operands(GemmArgs& g, int ta, int tb, int M, int N, int K, const void* A, long lda, const void* B, long ldb, long esz,
+             bool extra_aligned = true) {
+    ASSL_REQUIRE((ta ? M : K) % 8 == 0 && (tb ? N : K) % 8 == 0);
+    if (!ASSL_ALIGNED16(A) || !ASSL_ALIGNED16(B) || lda % 8 || ldb % 8 || !extra_aligned) return ASSL_EALIGN;
+    const long a_ext = (ta ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K)) * esz;
+    const long b_ext = (tb ? ((long)(K - 1) * ldb + N) : ((long)(N - 1) * ldb + K)) * esz;
+    ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);
+    g = GemmArgs{};
+    g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
+    g.a_bytes = (unsigned)a_ext; g.b_bytes = (unsigned)b_ext;
+    g.keep_scale = 1.f; g.ksplit = 1;
+    return ASSL_OK;
 }
 
+}  // namespace
 
 extern "C" int audiossl_gemm_multi(int count, int trans_a, int trans_b, int M, const int* Nv, const int* K, float alpha,
                                    const void* const* A, const long* lda, const void* const* B, const long* ldb,
                                    void* const* C, const long* ldcv, int out_f32, int atomic, int ksplit, void* stream) {
     ASSL_REQUIRE(count >= 1 && count <= MAX_MULTI && Nv && K && A && B && C && lda && ldb && ldcv && M > 0 && ksplit >= 1);
-    int N = 0;                                               // widest problem: sizes the grid, narrower ones leave blocks idle
-    for (int i = 0; i < count; ++i) { ASSL_REQUIRE(Nv[i] > 0); N = max(N, Nv[i]); }
+    for (int i = 0; i < count; ++i) ASSL_REQUIRE(Nv[i] > 0);
     ASSL_REQUIRE(atomic >= 0 && atomic <= 2);
     ASSL_REQUIRE(!atomic || out_f32);
     ASSL_REQUIRE(ksplit == 1 || atomic == 1);
     GemmMulti gm;
-    int kmin = 1 << 30;
     for (int i = 0; i < count; ++i) {
+        GemmArgs& g = gm.p[i];
         ASSL_REQUIRE(A[i] && B[i] && C[i] && K[i] > 0);
-        ASSL_REQUIRE((trans_a ? M : K[i]) % 8 == 0 && (trans_b ? Nv[i] : K[i]) % 8 == 0);
-        if (!ASSL_ALIGNED16(A[i]) || !ASSL_ALIGNED16(B[i]) || lda[i] % 8 || ldb[i] % 8) return ASSL_EALIGN;
-        const long a_ext = (trans_a ? ((long)(K[i] - 1) * lda[i] + M) : ((long)(M - 1) * lda[i] + K[i])) * 2;
-        const long b_ext = (trans_b ? ((long)(K[i] - 1) * ldb[i] + Nv[i]) : ((long)(Nv[i] - 1) * ldb[i] + K[i])) * 2;
-        ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);
-        gm.p[i] = GemmArgs{A[i], B[i], C[i], M, Nv[i], K[i], lda[i], ldb[i], ldcv[i], alpha, nullptr, 0, nullptr, 0, 1.f, nullptr, 0,
-                           out_f32, atomic, ksplit, nullptr, 0, (unsigned)a_ext, (unsigned)b_ext, 0};
-        gm.p[i].vec_epi = epi_vectorisable(gm.p[i], 1);
-        kmin = min(kmin, K[i]);
+        if (const int rc = operands(g, trans_a, trans_b, M, Nv[i], K[i], A[i], lda[i], B[i], ldb[i], 2)) return rc;
+        g.C = C[i]; g.ldc = ldcv[i]; g.alpha = alpha;
+        g.out_f32 = out_f32; g.atomic = atomic; g.ksplit = ksplit;
+        g.vec_epi = epi_vectorisable(g, 1);
     }
-    return dispatch_multi(gm, count, M, N, kmin, ksplit, trans_a, trans_b, static_cast<hipStream_t>(stream), K, Nv);
+    return run_multi(gm, count, trans_a, trans_b, Nv, K, static_cast<hipStream_t>(stream));
 }
 
 // Weight gradients that are applied where they are produced: G_i = alpha * op(A_i) op(B_i) is the gradient of parameter P_i ([M][N_i]
@@ -1768,28 +1752,21 @@ extern "C" int audiossl_gemm_multi_sgd(int count, int trans_a, int trans_b, int 
                                        float* const* P, float* const* Mom, void* const* Shadow, const long* ldp, float lr, float momentum,
                                        float weight_decay, float grad_scale, const float* grad_scale_dev, void* stream) {
     ASSL_REQUIRE(count >= 1 && count <= MAX_MULTI && Nv && K && A && B && P && Mom && lda && ldb && ldp && M > 0);
-    int N = 0;
-    for (int i = 0; i < count; ++i) { ASSL_REQUIRE(Nv[i] > 0); N = max(N, Nv[i]); }
+    for (int i = 0; i < count; ++i) ASSL_REQUIRE(Nv[i] > 0);
     GemmMulti gm;
-    int kmin = 1 << 30;
     for (int i = 0; i < count; ++i) {
+        GemmArgs& g = gm.p[i];
         ASSL_REQUIRE(A[i] && B[i] && P[i] && Mom[i] && K[i] > 0);
-        ASSL_REQUIRE((trans_a ? M : K[i]) % 8 == 0 && (trans_b ? Nv[i] : K[i]) % 8 == 0);
-        if (!ASSL_ALIGNED16(A[i]) || !ASSL_ALIGNED16(B[i]) || lda[i] % 8 || ldb[i] % 8) return ASSL_EALIGN;
-        if (!ASSL_ALIGNED16(P[i]) || !ASSL_ALIGNED16(Mom[i]) || ldp[i] % 8 || Nv[i] % 8) return ASSL_EALIGN;
         void* sh = Shadow ? Shadow[i] : nullptr;
-        if (sh && !ASSL_ALIGNED16(sh)) return ASSL_EALIGN;
-        const long a_ext = (trans_a ? ((long)(K[i] - 1) * lda[i] + M) : ((long)(M - 1) * lda[i] + K[i])) * 2;
-        const long b_ext = (trans_b ? ((long)(K[i] - 1) * ldb[i] + Nv[i]) : ((long)(Nv[i] - 1) * ldb[i] + K[i])) * 2;
-        ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);
-        gm.p[i] = GemmArgs{A[i], B[i], P[i], M, Nv[i], K[i], lda[i], ldb[i], ldp[i], alpha, nullptr, 0, nullptr, 0, 1.f, nullptr, 0,
-                           1, 0, 1, nullptr, 0, (unsigned)a_ext, (unsigned)b_ext, 0};
-        gm.p[i].vec_epi = epi_vectorisable(gm.p[i], 1);
-        gm.p[i].sgd_p = P[i]; gm.p[i].sgd_m = Mom[i]; gm.p[i].sgd_s = static_cast<bf16*>(sh); gm.p[i].sgd_gs_dev = grad_scale_dev;
-        gm.p[i].sgd_lr = lr; gm.p[i].sgd_mu = momentum; gm.p[i].sgd_wd = weight_decay; gm.p[i].sgd_gs = grad_scale;
-        kmin = min(kmin, K[i]);
+        if (const int rc = operands(g, trans_a, trans_b, M, Nv[i], K[i], A[i], lda[i], B[i], ldb[i], 2,
+                      ASSL_ALIGNED16(P[i]) && ASSL_ALIGNED16(Mom[i]) && ldp[i] % 8 == 0 && Nv[i] % 8 == 0 && ASSL_ALIGNED16(sh))) return rc;
+        g.C = P[i]; g.ldc = ldp[i]; g.alpha = alpha;
+        g.out_f32 = 1;
+        g.vec_epi = epi_vectorisable(g, 1);
+        g.sgd_p = P[i]; g.sgd_m = Mom[i]; g.sgd_s = static_cast<bf16*>(sh); g.sgd_gs_dev = grad_scale_dev;
+        g.sgd_lr = lr; g.sgd_mu = momentum; g.sgd_wd = weight_decay; g.sgd_gs = grad_scale;
     }
-    return dispatch_multi(gm, count, M, N, kmin, 1, trans_a, trans_b, static_cast<hipStream_t>(stream), K, Nv);
+    return run_multi(gm, count, trans_a, trans_b, Nv, K, static_cast<hipStream_t>(stream));
 }
 
 // The Barlow-twins cross-correlation of several heads, c_h = alpha * A_h^T B_h (A_h, B_h: [K_h][M] / [K_h][N] row-major, i.e. the
@@ -1801,109 +1778,18 @@ extern "C" int audiossl_gemm_multi_barlow(int count, int D, const int* K, float 
                                           float* const* loss_rep, void* stream) {
     ASSL_REQUIRE(count >= 1 && count <= MAX_MULTI && K && A && B && dc && lda && ldb && coef && dscale && loss_rep && D > 0 && D % 64 == 0);
     GemmMulti gm;
-    int kmin = 1 << 30;
     int Nv[MAX_MULTI];
     for (int i = 0; i < count; ++i) {
+        GemmArgs& g = gm.p[i];
         ASSL_REQUIRE(A[i] && B[i] && dc[i] && loss_rep[i] && K[i] > 0 && K[i] % 8 == 0);
-        if (!ASSL_ALIGNED16(A[i]) || !ASSL_ALIGNED16(B[i]) || !ASSL_ALIGNED16(dc[i]) || lda[i] % 8 || ldb[i] % 8) return ASSL_EALIGN;
-        const long a_ext = ((long)(K[i] - 1) * lda[i] + D) * 2, b_ext = ((long)(K[i] - 1) * ldb[i] + D) * 2;
-        ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);
-        gm.p[i] = GemmArgs{A[i], B[i], dc[i], D, D, K[i], lda[i], ldb[i], D, alpha, nullptr, 0, nullptr, 0, 1.f, nullptr, 0,
-                           0, 0, 1, nullptr, 0, (unsigned)a_ext, (unsigned)b_ext, 0};
-        gm.p[i].vec_epi = epi_vectorisable(gm.p[i], 1);
-        ASSL_REQUIRE(gm.p[i].vec_epi);
-        gm.p[i].bl_mode = 1; gm.p[i].bl_loss = loss_rep[i]; gm.p[i].bl_coef = coef[i]; gm.p[i].bl_dscale = dscale[i];
-        kmin = min(kmin, K[i]);
+        if (const int rc = operands(g, 1, 1, D, D, K[i], A[i], lda[i], B[i], ldb[i], 2, ASSL_ALIGNED16(dc[i]))) return rc;
+        g.C = dc[i]; g.ldc = D; g.alpha = alpha;
+        g.vec_epi = epi_vectorisable(g, 1);
+        ASSL_REQUIRE(g.vec_epi);
+        g.bl_mode = 1; g.bl_loss = loss_rep[i]; g.bl_coef = coef[i]; g.bl_dscale = dscale[i];
         Nv[i] = D;
     }
-    return dispatch_multi(gm, count, D, D, kmin, 1, 1, 1, static_cast<hipStream_t>(stream), K, Nv);
-}
-
-// kernel choice for bf16 operands (measured rules, see the comments inside)
-static int run_bf16(const GemmArgs& g, int trans_a, int trans_b, hipStream_t s) {
-    const int M = g.M, N = g.N, K = g.K, ksplit = g.ksplit;
-    const long blocks = (long)ceil_div(M, BM) * ceil_div(N, BN) * ksplit;
-    // AUDIOSSL_GEMM_RING = 10 * MI + NST forces one ring variant (tools/gemm_shapes.py sweeps them); 0 disables the ring
-    static const int ring = getenv("AUDIOSSL_GEMM_RING") ? atoi(getenv("AUDIOSSL_GEMM_RING")) : -1;
-    const bool ring_ok = K % GBK == 0 && M >= 8 && N >= 8;
-    static const int w8 = getenv("AUDIOSSL_GEMM_W8") ? atoi(getenv("AUDIOSSL_GEMM_W8")) : 0;
-    if (w8 && M >= 256) return dispatch<bf16, 64, 2, 8>(g, trans_a, trans_b, s);
-    // the hand-scheduled 256 x 256 kernel: AUDIOSSL_GEMM_P8 = 1 forces it wherever it is legal, 0 disables it
-    static const int p8 = getenv("AUDIOSSL_GEMM_P8") ? atoi(getenv("AUDIOSSL_GEMM_P8")) : -1;
-    const bool p8_ok = K % GBK == 0 && M >= 8 && N >= 8 && (!trans_a || M % 8 == 0) && (!trans_b || N % 8 == 0);
-    // transposed-A problems whose split-K launch fills the chip with 256 x 128 tiles: the software-pipelined kernel with the caller's
-    // split beats the 256 x 256 kernel with the split raised to fill the chip (the encoder's fc.3 weight gradient, 2048 x 2048 x 6144
-    // split in two: 97.4 -> 77.6 us, 664 TFLOP/s; AUDIOSSL_GEMM_P6=0 disables)
-    static const int p6_first = getenv("AUDIOSSL_GEMM_P6") ? atoi(getenv("AUDIOSSL_GEMM_P6")) : -1;
-    if (p6_first != 0 && p8 != 1 && p8_ok && trans_a && g.atomic == 1 && !g.lse_mode && M >= 256 && N >= 128) {
-        const long t6s = (long)ceil_div(M, 256) * ceil_div(N, 128) * ksplit;
-        if (t6s >= 192 && t6s <= 288 && K / ksplit >= 2048) return dispatch_sp<6>(g, trans_a, trans_b, s);
-    }
-    if (p8 != 0 && p8_ok && M >= 256 && N >= 256) {
-        // measured (tools/gemm_shapes.py, gemm_one.py): it wins once the 256 x 256 tiles occupy at least half of the CUs and every
-        // workgroup walks >= 16 K-tiles (6144 x 2048 x 2048 NT 83.9 -> 63.0 us with the bias / ReLU / dropout epilogue, NN 71.0 ->
-        // 60.4; 4096^3 214 -> 127 us, 8192^3 1.30 PFLOP/s); with few K-tiles its one-workgroup-per-CU epilogue is exposed
-        // (6144 x 2048 x 512: 30.8 vs 27.2 us) and on small grids the 128-row kernels spread over more CUs.
-        const long t256 = (long)ceil_div(M, 256) * ceil_div(N, 256);
-        GemmArgs ga = g;
-        if (g.atomic == 1 && t256 * ksplit < 192) {                  // accumulating outputs: split K until the chip is full
-            int ks = ksplit;
-            while (t256 * ks * 2 <= 256 && K / (ks * 2) >= 1024) ks *= 2;
-            ga.ksplit = ks;
-        }
-        const bool layout_ok = p8 != 2 || (!trans_a && !trans_b);            // AUDIOSSL_GEMM_P8=2: K-contiguous operands only
-        // ... and with 12 K-tiles once the grid is several rounds deep (the transformer blocks' K = 768 layers at 27,648 rows:
-        // 27648 x 2304 x 768 NT 188.6 -> 140.5 us, x 3072 235.3 -> 181.2, x 768 63.9 -> 53.2 against the K-step-32 kernel)
-        const bool deep = t256 * ga.ksplit >= 512 && K / ga.ksplit >= 768;
-        if (p8 == 1 || (layout_ok && t256 * ga.ksplit >= 128 && (K / ga.ksplit >= 1024 || deep)))
-            return sp_mask() & 8 ? dispatch_sp<8>(ga, trans_a, trans_b, s) : dispatch_p8(ga, trans_a, trans_b, s);
-    }
-    // the hand-scheduled 256 x 128 kernel (written for the multi-problem launches of the projector heads, see dispatch_multi):
-    // single problems whose 256 x 128 tiles fill the chip once while the 256 x 256 tiles would leave half of it idle
-    static const int p6 = getenv("AUDIOSSL_GEMM_P6") ? atoi(getenv("AUDIOSSL_GEMM_P6")) : -1;
-    if (p6 != 0 && p8_ok && !g.lse_mode && M >= 128 && N >= 128) {
-        const long t5 = (long)ceil_div(M, 128) * ceil_div(N, 128) * ksplit, t6 = (long)ceil_div(M, 256) * ceil_div(N, 128) * ksplit,
-                   t8 = (long)ceil_div(M, 256) * ceil_div(N, 256) * ksplit;
-        if (M >= 256 && (p6 == 1 || (t6 >= 128 && t6 <= 288 && t8 < 128 && K / ksplit >= 512)))
-            return dispatch_sp<6>(g, trans_a, trans_b, s);
-        // measured (tools/gemm_shapes.py): NN 6144 x 512 x 2048 34.1 -> 25.8 us, TN 2048 x 512 x 6144 / 3 41.9 -> 32.2 us; with short K
-        // loops (2048 x 2048 x 512 TN: 19.3 vs 17.9 us) and for K-contiguous operands on <= 128 tiles (the ring kernel: 20.2 vs 21.7 us)
-        // the older kernels stay
-        if (p6 == 5 || (p6 != 1 && t5 >= 96 && t5 <= 288 && t6 < 128 && K / ksplit >= 1024 && (trans_a || trans_b || t5 > 128)))
-            return sp_mask() & 2 ? dispatch_sp<5>(g, trans_a, trans_b, s) : dispatch_pk<5>(g, trans_a, trans_b, s);
-    }
-    // grids of >= 2 workgroups per CU with a K-contiguous A operand: K-step 32 and THREE co-resident workgroups per CU (41 KB
-    // of LDS each, 126 VGPRs) - 12 waves per CU hide the staged-load and barrier waits better than two workgroups at K-step
-    // 64 (6144x2048x2048 NT 80.9 -> 71.5 us, NN 90.2 -> 76.8 us; with a transposed A operand it measured slower)
-    static const int bk32 = getenv("AUDIOSSL_GEMM_BK32") ? atoi(getenv("AUDIOSSL_GEMM_BK32")) : 1;
-    if (bk32 && (!trans_a || bk32 == 2) && (long)ceil_div(M, BM) * ceil_div(N, BN) * ksplit >= 512)
-        return dispatch_bk32(g, trans_a, trans_b, s);
-    static const int t256 = getenv("AUDIOSSL_GEMM_T256") ? atoi(getenv("AUDIOSSL_GEMM_T256")) : 0;
-    if (t256 && M >= 1024 && N >= 512) return dispatch256(g, trans_a, trans_b, s);
-    if (ring_ok && ring > 0) {
-        switch (ring) {
-            case 12: return dispatch_ring<1, 2>(g, trans_a, trans_b, s);
-            case 13: return dispatch_ring<1, 3>(g, trans_a, trans_b, s);
-            case 14: return dispatch_ring<1, 4>(g, trans_a, trans_b, s);
-            case 16: return dispatch_ring<1, 6>(g, trans_a, trans_b, s);
-            case 22: return dispatch_ring<2, 2>(g, trans_a, trans_b, s);
-            case 23: return dispatch_ring<2, 3>(g, trans_a, trans_b, s);
-            case 24: return dispatch_ring<2, 4>(g, trans_a, trans_b, s);
-            default: break;
-        }
-    }
-    // measured (tools/gemm_shapes.py): the ring wins for K-contiguous operands (NT) on grids of at most two waves of
-    // workgroups - 64-row tiles up to 128 full tiles, 128-row tiles up to 512; with a transposed operand or on larger grids
-    // two co-resident workgroups of the register-staged kernel overlap each other better
-    if (ring_ok && ring < 0 && !trans_a && !trans_b) {
-        if (blocks <= 128 && M > 64) return dispatch_ring<1, 4>(g, 0, 0, s);
-        if (blocks > 128 && blocks <= 512) return dispatch_ring<2, 4>(g, 0, 0, s);
-    }
-    static const bool small_tiles = getenv("AUDIOSSL_GEMM_SMALL") ? atoi(getenv("AUDIOSSL_GEMM_SMALL")) != 0 : true;
-    // these shapes are latency-bound per workgroup (~0.5 us per 64-deep k-step whatever the tile): when 128 x 128 tiles
-    // would occupy at most half of the 256 CUs, halve the tile in M and run twice as many workgroups
-    if (small_tiles && blocks <= 128 && M > 64) return dispatch<bf16, 64, 1>(g, trans_a, trans_b, s);
-    return blocks <= 256 && K >= 512 ? dispatch<bf16, 128, 2>(g, trans_a, trans_b, s) : dispatch<bf16, 64, 2>(g, trans_a, trans_b, s);
+    return run_multi(gm, count, 1, 1, Nv, K, static_cast<hipStream_t>(stream));
 }
 
 // dtype: 0 = fp32 operands (exact f32 MFMA), 1 = bf16 operands.  See include/audiossl_hip.h.
@@ -1919,21 +1805,20 @@ extern "C" int audiossl_gemm(int dtype, int trans_a, int trans_b, int M, int N, 
     ASSL_REQUIRE(ksplit == 1 || atomic == 1);
     ASSL_REQUIRE(ksplit == 1 || (!relu && !keep && !gate));             // non-linear epilogue terms need the whole sum (the bias is added by split 0)
     ASSL_REQUIRE(!resid || (ksplit == 1 && !atomic));
-    // vector (8-element) dimension of each operand must be a multiple of 8 and its rows 16-byte aligned
-    ASSL_REQUIRE((trans_a ? M : K) % 8 == 0 && (trans_b ? N : K) % 8 == 0);
-    if (!ASSL_ALIGNED16(A) || !ASSL_ALIGNED16(B) || lda % 8 || ldb % 8) return ASSL_EALIGN;
-    const long esz = dtype == 0 ? 4 : 2;
-    const long a_ext = (trans_a ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K)) * esz;
-    const long b_ext = (trans_b ? ((long)(K - 1) * ldb + N) : ((long)(N - 1) * ldb + K)) * esz;
-    ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);            // 32-bit buffer offsets
-    GemmArgs g{A, B, C, M, N, K, lda, ldb, ldc, alpha, bias, relu, keep, ldk, keep_scale, gate, ldg,
-               (dtype == 0) ? 1 : out_f32, atomic, ksplit, resid, ldr, (unsigned)a_ext, (unsigned)b_ext, 0};
+    GemmArgs g;
+    if (const int rc = operands(g, trans_a, trans_b, M, N, K, A, lda, B, ldb, dtype == 0 ? 4 : 2)) return rc;
+    g.C = C; g.ldc = ldc; g.alpha = alpha;
+    g.bias = bias; g.relu = relu; g.keep = keep; g.ldk = ldk; g.keep_scale = keep_scale; g.gate = gate; g.ldg = ldg;
+    g.out_f32 = (dtype == 0) ? 1 : out_f32; g.atomic = atomic; g.ksplit = ksplit; g.resid = resid; g.ldr = ldr;
     g.vec_epi = epi_vectorisable(g, dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == 0) return dispatch<float, 32, 2>(g, trans_a, trans_b, s);
-    return run_bf16(g, trans_a, trans_b, s);
+    if (dtype == 1) return run_bf16(g, trans_a, trans_b, s);
+    if (switches().bad) return ASSL_EINVAL;
+    // fp32 operands (the validation / high-precision path): one kernel
+    return by_layout(trans_a, trans_b, [&](auto a, auto b) {
+        return launch_single(reg_kernel<float, decltype(a)::value, decltype(b)::value, 32, 2>(), g, true, s);
+    });
 }
-
 
 // Linear -> ReLU -> Dropout of the encoder's first fully connected layer (`src/encoder/audiontt.py:62-66`) with the keep mask drawn in
 // the epilogue: C = dropout(relu(alpha * op(A) op(B) + bias)), element (row, col) kept iff dropout_keep(seed', row * N + col) with
@@ -1943,13 +1828,10 @@ extern "C" int audiossl_gemm_dropout(int trans_a, int trans_b, int M, int N, int
                                      const void* B, long ldb, void* C, long ldc, const float* bias, int relu,
                                      unsigned long long seed, float p, const long long* counter, float keep_scale, void* stream) {
     ASSL_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0 && p >= 0.f && p < 1.f);
-    ASSL_REQUIRE((trans_a ? M : K) % 8 == 0 && (trans_b ? N : K) % 8 == 0);
-    if (!ASSL_ALIGNED16(A) || !ASSL_ALIGNED16(B) || lda % 8 || ldb % 8) return ASSL_EALIGN;
-    const long a_ext = (trans_a ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K)) * 2;
-    const long b_ext = (trans_b ? ((long)(K - 1) * ldb + N) : ((long)(N - 1) * ldb + K)) * 2;
-    ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);
-    GemmArgs g{A, B, C, M, N, K, lda, ldb, ldc, alpha, bias, relu, nullptr, 0, keep_scale, nullptr, 0,
-               0, 0, 1, nullptr, 0, (unsigned)a_ext, (unsigned)b_ext, 0};
+    GemmArgs g;
+    if (const int rc = operands(g, trans_a, trans_b, M, N, K, A, lda, B, ldb, 2)) return rc;
+    g.C = C; g.ldc = ldc; g.alpha = alpha;
+    g.bias = bias; g.relu = relu; g.keep_scale = keep_scale;
     g.vec_epi = epi_vectorisable(g, 1);
     g.drop_on = 1;
     g.drop_thr = (unsigned int)fminf(p * 4294967296.f, 4294967295.f);
@@ -1966,11 +1848,9 @@ extern "C" int audiossl_moco_logits(int mode, const void* qn, const void* queue,
                                     const float* lse, float gscale, void* P, void* stream) {
     ASSL_REQUIRE(qn && queue && B > 0 && K > 0 && dim > 0 && (mode == 1 || mode == 2));
     ASSL_REQUIRE(mode == 1 ? part != nullptr : (lse != nullptr && P != nullptr));
-    ASSL_REQUIRE(dim % 8 == 0 && K % 8 == 0);
-    if (!ASSL_ALIGNED16(qn) || !ASSL_ALIGNED16(queue) || (P && !ASSL_ALIGNED16(P))) return ASSL_EALIGN;
-    const long a_ext = ((long)(B - 1) * dim + dim) * 2, b_ext = ((long)(dim - 1) * K + K) * 2;
-    ASSL_REQUIRE(a_ext < 0xFFFFFF00L && b_ext < 0xFFFFFF00L);
-    GemmArgs g{qn, queue, P, B, K, dim, dim, K, K, inv_t, nullptr, 0, nullptr, 0, 1.f, nullptr, 0,
-               0, 0, 1, nullptr, 0, (unsigned)a_ext, (unsigned)b_ext, 0, 0, mode, part, lse, gscale, ceil_div(K, 64)};
+    GemmArgs g;
+    if (const int rc = operands(g, 0, 1, B, K, dim, qn, dim, queue, K, 2, ASSL_ALIGNED16(P))) return rc;
+    g.C = P; g.ldc = K; g.alpha = inv_t;
+    g.lse_mode = mode; g.part = part; g.lse = lse; g.gscale = gscale; g.nslot = ceil_div(K, 64);
     return run_bf16(g, 0, 1, static_cast<hipStream_t>(stream));
 }

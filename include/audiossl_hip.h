@@ -316,7 +316,7 @@ int audiossl_ema_update(float* pk, const float* pq, long n, float m, void* shado
  * scratch arena with one memset), so they skip their own hipMemsetAsync; 0 (default) = they zero their scratch themselves. */
 int audiossl_set_prezeroed(int on);
 /* Host-side query (diagnostics): the kernel the most recent audiossl_gemm / gemm_multi / gemm_multi_barlow / moco_logits call
- * launched, as a substring of the name rocprofv3 prints for it ("gemm_p6_multi_kernel<false, false>"; instantiations on the bf16
+ * launched, as a substring of the name rocprofv3 prints for it ("gemm_sp_multi_kernel<false, false, 6>"; instantiations on the bf16
  * type appear mangled there: "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E").  The dispatch picks among several instantiations
  * by shape; bench.py's per-kernel roofline table uses this to join its rows to profiles/ kernel_stats.csv. */
 int audiossl_last_kernel(char* name, int capacity);

@@ -825,6 +825,7 @@ def test_gemm_multi_sgd_epilogue_equals_gemm_then_sgd(N):
 _VARIANT_SCRIPT = r"""
 import sys, torch
 sys.path[:0] = [{root!r}, {pkg!r}]
+from src import _native as N
 from src import engine as E
 torch.manual_seed(0)
 worst = 0.0
@@ -834,53 +835,270 @@ for mode, M, Nn, K in {shapes!r}:
     B = torch.randn((K, Nn) if tb else (Nn, K), device="cuda").bfloat16()
     C = torch.empty(M, Nn, device="cuda", dtype=torch.float32)
     E.gemm(1, ta, tb, M, Nn, K, A, A.shape[1], B, B.shape[1], C, Nn, out_f32=1)
+    print("KERNEL", mode, N.last_kernel())
     torch.cuda.synchronize()
     ref = (A.float().t() if ta else A.float()) @ (B.float() if tb else B.float().t())
     worst = max(worst, float((C - ref).norm() / ref.norm()))
 print("WORST", worst)
 """
 
+_MISSPELT_SCRIPT = r"""
+import sys, torch
+sys.path[:0] = [{root!r}, {pkg!r}]
+from src import _native as N
+a = torch.zeros(16, 16, device="cuda")
+p = a.data_ptr()
+print("RC", N.lib().audiossl_gemm(0, 0, 0, 16, 16, 16, 1.0, p, 16, p, 16, p, 16, None, 0, None, 0, 1.0, None, 0, 1, 0, 1, None, 0, None))
+"""
 
-@pytest.mark.parametrize("env,shapes", [
-    ({"AUDIOSSL_GEMM_RING": "24"}, [("NT", 300, 264, 128), ("NN", 300, 264, 128), ("TN", 296, 264, 128)]),
-    ({"AUDIOSSL_GEMM_RING": "13"}, [("NT", 300, 264, 192), ("NN", 300, 264, 192), ("TN", 296, 264, 192)]),
-    ({"AUDIOSSL_GEMM_T256": "1"}, [("NT", 1100, 520, 128), ("NN", 1100, 520, 128), ("TN", 1096, 520, 128)]),
-    ({"AUDIOSSL_GEMM_W8": "1"}, [("NT", 300, 264, 128), ("NN", 300, 264, 128), ("TN", 296, 264, 128)]),
-    ({"AUDIOSSL_GEMM_BK32": "2"}, [("NT", 2048, 4096, 96), ("NN", 2048, 4096, 96), ("TN", 2048, 4096, 96)]),
-    # hand-scheduled 256 x 256 kernel: one K-tile, an odd and an even number of K-tiles, partial tiles in M and N
-    ({"AUDIOSSL_GEMM_P8": "1"}, [("NT", 1100, 520, 64), ("NT", 1100, 520, 192), ("NT", 700, 264, 512), ("NN", 1100, 520, 192),
-                                 ("NN", 700, 264, 512), ("TN", 1096, 520, 192), ("TN", 696, 264, 512), ("NT", 6144, 2048, 2048),
-                                 ("NN", 1024, 2048, 1024), ("TN", 2048, 520, 1024)]),
-    # software-pipelined 256 x 128 kernel (ring of three 48 KB stages): 1, 2, 3, 4 and 7 K-tiles, partial tiles in M and N, the heads' shapes
-    ({"AUDIOSSL_GEMM_P6": "1", "AUDIOSSL_GEMM_P8": "0"},
-     [("NT", 1100, 392, 64), ("NT", 1100, 392, 128), ("NT", 700, 264, 192), ("NT", 520, 136, 256), ("NN", 1100, 392, 192),
-      ("NN", 700, 264, 448), ("NN", 300, 200, 320), ("TN", 1096, 392, 192), ("TN", 696, 264, 448), ("TN", 296, 136, 128), ("NT", 1024, 2048, 2048),
-      ("NN", 1024, 2048, 2048), ("TN", 2048, 1024, 1024)]),
-    # hand-scheduled 128 x 128 kernel (ring of five buffers): 1 ... 7 K-tiles, partial tiles, the heads' M = 512 shapes
-    ({"AUDIOSSL_GEMM_P6": "5", "AUDIOSSL_GEMM_P8": "0"},
-     [("NT", 600, 392, 64), ("NT", 600, 392, 128), ("NT", 300, 264, 192), ("NT", 520, 136, 256), ("NT", 130, 130, 320), ("NN", 600, 392, 384),
-      ("NN", 300, 264, 448), ("TN", 600, 392, 192), ("TN", 296, 264, 448), ("NT", 512, 2048, 2048), ("NN", 512, 2048, 2048),
-      ("NN", 6144, 512, 2048)]),
-    # the software-pipelined form of the 256 x 256 tile (BK 32, ring of five) and of the 128 x 128 tile (BK 64, ring of five): not the
-    # default for these tiles (gemm.hip, sp_mask), kept selectable - every layout, 1 ... 7 K-tiles, partial tiles
-    ({"AUDIOSSL_GEMM_SP": "8", "AUDIOSSL_GEMM_P8": "1"},
-     [("NT", 1100, 520, 64), ("NT", 1100, 520, 192), ("NT", 700, 264, 512), ("NN", 1100, 520, 192), ("NN", 700, 264, 512),
-      ("TN", 1096, 520, 192), ("TN", 696, 264, 512), ("NT", 6144, 2048, 2048), ("TN", 2048, 520, 1024)]),
-    ({"AUDIOSSL_GEMM_SP": "2", "AUDIOSSL_GEMM_P6": "5", "AUDIOSSL_GEMM_P8": "0"},
-     [("NT", 600, 392, 64), ("NT", 600, 392, 128), ("NT", 300, 264, 192), ("NT", 130, 130, 320), ("NN", 600, 392, 384),
-      ("NN", 300, 264, 448), ("TN", 600, 392, 192), ("TN", 296, 264, 448), ("NT", 512, 2048, 2048)]),
-])
-def test_gemm_tile_variants_in_subprocess(env, shapes):
-    """The tile variants that the default dispatch does not pick for these shapes (ring of every layout, 256x256 and 256x128
-    8-wave tiles, K-step 32 with a transposed A) stay correct: each is forced through its environment switch in a child
-    process (the switches are read once per process) on shapes with partial tiles."""
+
+def _gemm_child(script, env, **fmt):
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = _VARIANT_SCRIPT.format(root=root, pkg=os.path.join(root, "audio-ssl_amd"), shapes=shapes)
+    code = script.format(root=root, pkg=os.path.join(root, "audio-ssl_amd"), **fmt)
     out = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
-    worst = float(out.stdout.strip().split("WORST")[-1])
-    assert worst < 1e-5, (env, worst)
+    return out.stdout
+
+
+_misspelt_rc = []           # the return code of the first audiossl_gemm call under a misspelt switch (one child per session)
+
+# AUDIOSSL_GEMM_FORCE value -> the kernel every launch of the row must report ({a}, {b}: the layout's TA / TB)
+_FORCED_KERNEL = {"ring64": "gemm_ring_kernel<{a}, {b}, 1, 4>", "ring128": "gemm_ring_kernel<{a}, {b}, 2, 4>", "bk32": "gemm_bk32_kernel<{a}, {b}>",
+                  "p8": "gemm_p8_kernel<{a}, {b}, 0>", "pk5": "gemm_pk_kernel<{a}, {b}, 5>", "sp5": "gemm_sp_kernel<{a}, {b}, 5>",
+                  "sp6": "gemm_sp_kernel<{a}, {b}, 6>", "sp8": "gemm_sp_kernel<{a}, {b}, 8>"}
+
+
+@pytest.mark.parametrize("env,shapes", [
+    ({"AUDIOSSL_GEMM_FORCE": "ring128"}, [("NT", 300, 264, 128), ("NN", 300, 264, 128), ("TN", 296, 264, 128)]),
+    # K = 192 is three K-tiles against the ring of four: the short prologue
+    ({"AUDIOSSL_GEMM_FORCE": "ring64"}, [("NT", 300, 264, 192), ("NN", 300, 264, 192), ("TN", 296, 264, 192)]),
+    ({"AUDIOSSL_GEMM_FORCE": "bk32"}, [("NT", 2048, 4096, 96), ("NN", 2048, 4096, 96), ("TN", 2048, 4096, 96)]),
+    # hand-scheduled 256 x 256 kernel: one K-tile, an odd and an even number of K-tiles, partial tiles in M and N
+    ({"AUDIOSSL_GEMM_FORCE": "p8"}, [("NT", 1100, 520, 64), ("NT", 1100, 520, 192), ("NT", 700, 264, 512), ("NN", 1100, 520, 192),
+            ("NN", 700, 264, 512), ("TN", 1096, 520, 192), ("TN", 696, 264, 512), ("NT", 6144, 2048, 2048),
+            ("NN", 1024, 2048, 1024), ("TN", 2048, 520, 1024)]),
+    # software-pipelined 256 x 128 kernel (ring of three 48 KB stages): 1, 2, 3, 4 and 7 K-tiles, partial tiles in M and N, the heads' shapes
+    ({"AUDIOSSL_GEMM_FORCE": "sp6"}, [("NT", 1100, 392, 64), ("NT", 1100, 392, 128), ("NT", 700, 264, 192), ("NT", 520, 136, 256), ("NN", 1100, 392, 192),
+             ("NN", 700, 264, 448), ("NN", 300, 200, 320), ("TN", 1096, 392, 192), ("TN", 696, 264, 448), ("TN", 296, 136, 128),
+             ("NT", 1024, 2048, 2048), ("NN", 1024, 2048, 2048), ("TN", 2048, 1024, 1024)]),
+    # hand-scheduled 128 x 128 kernel (ring of five buffers): 1 ... 7 K-tiles, partial tiles, the heads' M = 512 shapes
+    ({"AUDIOSSL_GEMM_FORCE": "pk5"}, [("NT", 600, 392, 64), ("NT", 600, 392, 128), ("NT", 300, 264, 192), ("NT", 520, 136, 256), ("NT", 130, 130, 320),
+             ("NN", 600, 392, 384), ("NN", 300, 264, 448), ("TN", 600, 392, 192), ("TN", 296, 264, 448), ("NT", 512, 2048, 2048),
+             ("NN", 512, 2048, 2048), ("NN", 6144, 512, 2048)]),
+    # the software-pipelined form of the 256 x 256 tile (BK 32, ring of five) and of the 128 x 128 tile (BK 64, ring of five): not the
+    # default for these tiles (gemm.hip, SpBody), kept selectable - every layout, 1 ... 7 K-tiles, partial tiles
+    ({"AUDIOSSL_GEMM_FORCE": "sp8"}, [("NT", 1100, 520, 64), ("NT", 1100, 520, 192), ("NT", 700, 264, 512), ("NN", 1100, 520, 192), ("NN", 700, 264, 512),
+             ("TN", 1096, 520, 192), ("TN", 696, 264, 512), ("NT", 6144, 2048, 2048), ("TN", 2048, 520, 1024)]),
+    ({"AUDIOSSL_GEMM_FORCE": "sp5"}, [("NT", 600, 392, 64), ("NT", 600, 392, 128), ("NT", 300, 264, 192), ("NT", 130, 130, 320), ("NN", 600, 392, 384),
+             ("NN", 300, 264, 448), ("TN", 600, 392, 192), ("TN", 296, 264, 448), ("NT", 512, 2048, 2048)]),
+    # ids: the rows keep the positions they have had all along (2 and 3 were the AUDIOSSL_GEMM_T256 / _W8 rows, gone with their kernels)
+], ids=["env0-shapes0", "env1-shapes1", "env4-shapes4", "env5-shapes5", "env6-shapes6", "env7-shapes7", "env8-shapes8", "env9-shapes9"])
+def test_gemm_tile_variants_in_subprocess(env, shapes):
+    """The tile variants that the default dispatch does not pick for these shapes (ring of every layout, K-step 32 with a
+    transposed A, the hand-scheduled and software-pipelined tiles) stay correct: each is forced through AUDIOSSL_GEMM_FORCE in a
+    child process (the switches are read once per process) on shapes with partial tiles, and every launch reports the forced
+    family's kernel - every shape is legal for its variant, so none may fall back to the default choice.  A misspelt variant
+    name must not run the default either: the first GEMM call returns ASSL_EINVAL (-1)."""
+    variant = env["AUDIOSSL_GEMM_FORCE"]
+    out = _gemm_child(_VARIANT_SCRIPT, env, shapes=shapes)
+    ran = [ln.split(" ", 2)[1:] for ln in out.splitlines() if ln.startswith("KERNEL ")]
+    assert len(ran) == len(shapes)
+    for (mode, name), shape in zip(ran, shapes):
+        a, b = {"NT": ("false", "false"), "NN": ("false", "true"), "TN": ("true", "true")}[mode]
+        assert name == _FORCED_KERNEL[variant].format(a=a, b=b), (variant, shape, name)
+    worst = float(out.strip().split("WORST")[-1])
+    assert worst < 1e-5, (variant, worst)
+    if not _misspelt_rc:
+        _misspelt_rc.append(int(_gemm_child(_MISSPELT_SCRIPT, {"AUDIOSSL_GEMM_FORCE": "nonsense"}).split("RC")[-1]))
+    assert _misspelt_rc[0] == -1
+
+
+_H3, _KIN = (2048, 2048, 2048), (2048, 1024, 512)
+# (entry, layout, M, N or per-problem Ns, K or per-problem Ks, out_f32, atomic, ksplit, epilogue flags, kernel); moco_logits: M, N, K = B, queue
+# length, dim.  Where a bound cannot be met from both sides it has no row: with <= 127 tiles of 256 x 256 there are at most 254 of 256 x 128 and
+# of 128 x 128 (the upper bounds of 288), and the split-K raise starts below 192 workgroups but only ever acts at <= 128.
+_DISPATCH_PIN = [
+    # ---- tools/gemm_shapes.py: SHAPES (split / accumulation mode as the tool derives them)
+    ("gemm", "NT", 1024, 2048, 2048, 0, 0, 1, "", "gemm_ring_kernel<false, false, 1, 4>"),
+    ("gemm", "NT", 6144, 2048, 512, 0, 0, 1, "bias relu keep", "gemm_bk32_kernel<false, false>"),
+    ("gemm", "NT", 6144, 2048, 2048, 0, 0, 1, "bias relu keep", "gemm_p8_kernel<false, false, 0>"),
+    ("gemm", "NT", 512, 2048, 2048, 0, 0, 1, "", "gemm_ring_kernel<false, false, 1, 4>"),
+    ("gemm", "NT", 512, 128, 2048, 0, 0, 1, "", "gemm_ring_kernel<false, false, 1, 4>"),
+    ("gemm", "NT", 512, 128, 65536, 1, 1, 32, "", "gemm_ring_kernel<false, false, 1, 4>"),
+    ("gemm", "NN", 1024, 2048, 2048, 1, 0, 1, "", "gemm_pk_kernel<false, true, 5>"),
+    ("gemm", "NN", 6144, 2048, 2048, 0, 0, 1, "gate", "gemm_p8_kernel<false, true, 0>"),
+    ("gemm", "NN", 512, 2048, 2048, 1, 0, 1, "", "gemm_kernelIDF16bLb0ELb1ELi64ELi1ELi4E"),
+    ("gemm", "NN", 6144, 512, 2048, 1, 0, 1, "", "gemm_pk_kernel<false, true, 5>"),
+    ("gemm", "NN", 512, 65536, 128, 1, 0, 1, "", "gemm_bk32_kernel<false, true>"),
+    ("gemm", "TN", 2048, 2048, 1024, 1, 2, 1, "", "gemm_sp_kernel<true, true, 6>"),
+    ("gemm", "TN", 2048, 2048, 6144, 1, 1, 2, "", "gemm_sp_kernel<true, true, 6>"),
+    ("gemm", "TN", 2048, 2048, 512, 1, 2, 1, "", "gemm_sp_kernel<true, true, 6>"),
+    ("gemm", "TN", 2048, 512, 6144, 1, 1, 3, "", "gemm_pk_kernel<true, true, 5>"),
+    ("gemm", "TN", 2048, 2048, 512, 1, 0, 1, "", "gemm_sp_kernel<true, true, 6>"),
+    # ---- tools/heads_gemm_bench.py: LAUNCHES
+    ("gemm_multi", "NT", 1024, _H3, _KIN, 0, 0, 1, "", "gemm_sp_multi_kernel<false, false, 6>"),
+    ("gemm_multi", "NT", 1024, _H3, _H3, 0, 0, 1, "", "gemm_sp_multi_kernel<false, false, 6>"),
+    ("gemm_multi", "NT", 512, _H3, _H3, 1, 0, 1, "", "gemm_pk_multi_kernel<false, false, 5>"),
+    ("gemm_multi", "NN", 512, _H3, _H3, 1, 0, 1, "", "gemm_pk_multi_kernel<false, true, 5>"),
+    ("gemm_multi", "NN", 1024, _H3, _H3, 1, 0, 1, "", "gemm_sp_multi_kernel<false, true, 6>"),
+    ("gemm_multi", "NN", 512, _KIN, _H3, 1, 0, 1, "", "gemm_pk_multi_kernel<false, true, 5>"),
+    ("gemm_multi", "TN", 2048, _H3, (1024, 1024, 1024), 1, 0, 1, "", "gemm_p8_multi_kernel<true, true>"),
+    ("gemm_multi", "TN", 2048, _KIN, (1024, 1024, 1024), 1, 0, 1, "", "gemm_sp_multi_kernel<true, true, 6>"),
+    ("gemm_multi", "TN", 2048, _H3, (512, 512, 512), 1, 0, 1, "", "gemm_p8_multi_kernel<true, true>"),
+    # ---- tools/wgrad_sgd_bench.py: the fused weight-gradient + SGD launches
+    ("gemm_multi_sgd", "TN", 2048, _H3, (1024, 1024, 1024), 1, 0, 1, "", "gemm_p8_multi_sgd_kernel<true, true>"),
+    ("gemm_multi_sgd", "TN", 2048, _KIN, (1024, 1024, 1024), 1, 0, 1, "", "gemm_sp_multi_sgd_kernel<true, true, 6>"),
+    # ---- the encoder's Linear -> ReLU -> Dropout, the MoCo logits, the transformer blocks, one fp32 problem
+    ("gemm_dropout", "NT", 6144, 2048, 512, 0, 0, 1, "bias relu", "gemm_bk32_kernel<false, false>"),
+    ("moco_logits", "NN", 512, 65536, 128, 0, 0, 1, "mode1", "gemm_bk32_kernel<false, true>"),
+    ("moco_logits", "NN", 512, 65536, 128, 0, 0, 1, "mode2", "gemm_bk32_kernel<false, true>"),
+    ("gemm", "NT", 27648, 2304, 768, 0, 0, 1, "", "gemm_p8_kernel<false, false, 0>"),
+    ("gemm", "NT", 27648, 3072, 768, 0, 0, 1, "", "gemm_p8_kernel<false, false, 0>"),
+    ("gemm", "NT", 27648, 768, 768, 0, 0, 1, "", "gemm_bk32_kernel<false, false>"),
+    ("gemm", "NT", 27648, 768, 3072, 0, 0, 1, "", "gemm_p8_kernel<false, false, 0>"),
+    ("gemm", "NT", 1024, 2048, 2048, 1, 0, 1, "fp32", "gemm_kernelIfLb0ELb0ELi32ELi2ELi4E"),
+    # ---- single problems: one shape on either side of every threshold of the choice function, in rule order
+    # split-K transposed-A problems on 256 x 128 tiles: 192 <= tiles <= 288, K / ksplit >= 2048
+    ("gemm", "TN", 2048, 1536, 4096, 1, 1, 2, "", "gemm_sp_kernel<true, true, 6>"),       # 192 tiles
+    ("gemm", "TN", 2048, 1408, 4096, 1, 1, 2, "", "gemm_p8_kernel<true, true, 0>"),       # 176
+    ("gemm", "TN", 2304, 2048, 4096, 1, 1, 2, "", "gemm_sp_kernel<true, true, 6>"),       # 288
+    ("gemm", "TN", 2560, 2048, 4096, 1, 1, 2, "", "gemm_p8_kernel<true, true, 0>"),       # 320
+    ("gemm", "TN", 2048, 2048, 4032, 1, 1, 2, "", "gemm_p8_kernel<true, true, 0>"),       # K / ksplit = 2016
+    # 256 x 256 tiles: >= 128 of them, K / ksplit >= 1024, or >= 512 tiles with K / ksplit >= 768; M, N >= 256
+    ("gemm", "NT", 4096, 2048, 1024, 0, 0, 1, "", "gemm_p8_kernel<false, false, 0>"),       # 128 tiles
+    ("gemm", "NT", 3840, 2048, 1024, 0, 0, 1, "", "gemm_sp_kernel<false, false, 6>"),       # 120
+    ("gemm", "NT", 4096, 2048, 960, 0, 0, 1, "", "gemm_bk32_kernel<false, false>"),        # K = 960
+    ("gemm", "NT", 8192, 4096, 768, 0, 0, 1, "", "gemm_p8_kernel<false, false, 0>"),        # 512 tiles, K = 768
+    ("gemm", "NT", 7936, 4096, 768, 0, 0, 1, "", "gemm_bk32_kernel<false, false>"),        # 496 tiles
+    ("gemm", "NT", 8192, 4096, 704, 0, 0, 1, "", "gemm_bk32_kernel<false, false>"),        # K = 704
+    ("gemm", "NT", 32768, 248, 1024, 0, 0, 1, "", "gemm_bk32_kernel<false, false>"),       # N < 256
+    ("gemm", "NT", 32768, 256, 1024, 0, 0, 1, "", "gemm_p8_kernel<false, false, 0>"),
+    ("gemm", "NN", 248, 32768, 1024, 0, 0, 1, "", "gemm_bk32_kernel<false, true>"),       # M < 256
+    ("gemm", "NN", 256, 32768, 1024, 0, 0, 1, "", "gemm_p8_kernel<false, true, 0>"),
+    # ... its split-K raise for accumulating outputs (tiles * ksplit < 192; doubled while <= 256 workgroups and K / ksplit >= 1024)
+    ("gemm", "TN", 1024, 1024, 8192, 1, 1, 1, "", "gemm_p8_kernel<true, true, 0>"),       # raised to 8: 128 workgroups, 1024 deep
+    ("gemm", "TN", 1024, 1024, 8128, 1, 1, 1, "", "gemm_kernelIDF16bLb1ELb1ELi64ELi1ELi4E"),       # raised to 4 only: 64 workgroups
+    ("gemm", "TN", 1024, 1024, 16384, 1, 1, 1, "", "gemm_p8_kernel<true, true, 0>"),      # raised to 16: 256 workgroups
+    ("gemm", "TN", 1280, 1024, 16384, 1, 1, 1, "", "gemm_p8_kernel<true, true, 0>"),      # 20 tiles: stops at 8 (160 workgroups)
+    ("gemm", "TN", 6144, 2048, 2048, 1, 1, 1, "", "gemm_p8_kernel<true, true, 0>"),       # 192 tiles: no raise
+    ("gemm", "TN", 5888, 2048, 2048, 1, 1, 1, "", "gemm_p8_kernel<true, true, 0>"),       # 184 tiles
+    # 256 x 128 tiles: 128 <= tiles <= 288 while the 256 x 256 tiles number < 128, K / ksplit >= 512, M >= 256
+    ("gemm", "NT", 2048, 2048, 2048, 0, 0, 1, "", "gemm_sp_kernel<false, false, 6>"),       # 128 tiles
+    ("gemm", "NT", 1792, 2048, 2048, 0, 0, 1, "", "gemm_pk_kernel<false, false, 5>"),       # 112
+    ("gemm", "NT", 3840, 2048, 512, 0, 0, 1, "", "gemm_sp_kernel<false, false, 6>"),        # 120 tiles of 256 x 256
+    ("gemm", "NT", 4096, 2048, 512, 0, 0, 1, "", "gemm_bk32_kernel<false, false>"),        # 128 tiles of 256 x 256 (also: 512 tiles of 128 x 128)
+    ("gemm", "NT", 2048, 2048, 512, 0, 0, 1, "", "gemm_sp_kernel<false, false, 6>"),        # K = 512
+    ("gemm", "NT", 2048, 2048, 448, 0, 0, 1, "", "gemm_ring_kernel<false, false, 2, 4>"),        # K = 448
+    ("gemm", "NN", 248, 16384, 1024, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb1ELi128ELi2ELi4E"),       # M < 256 with 128 tiles
+    # 128 x 128 tiles: 96 <= tiles <= 288 while the 256 x 128 tiles number < 128, K / ksplit >= 1024, a transposed operand or > 128 tiles
+    ("gemm", "NN", 512, 3072, 2048, 0, 0, 1, "", "gemm_pk_kernel<false, true, 5>"),        # 96 tiles
+    ("gemm", "NN", 512, 2944, 2048, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb1ELi64ELi1ELi4E"),        # 92
+    ("gemm", "NN", 248, 16256, 1024, 0, 0, 1, "", "gemm_pk_kernel<false, true, 5>"),       # 127 tiles of 256 x 128
+    ("gemm", "NN", 1024, 2048, 1024, 0, 0, 1, "", "gemm_pk_kernel<false, true, 5>"),       # K = 1024
+    ("gemm", "NN", 1024, 2048, 960, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb1ELi64ELi1ELi4E"),        # K = 960
+    ("gemm", "NT", 1152, 2048, 2048, 0, 0, 1, "", "gemm_pk_kernel<false, false, 5>"),       # K-contiguous operands, 144 tiles (128: the first row of this table)
+    ("gemm", "NN", 120, 16384, 1024, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb1ELi64ELi1ELi4E"),       # M < 128
+    ("gemm", "NN", 128, 16384, 1024, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb1ELi64ELi1ELi4E"),
+    # K-step 32: >= 512 tiles of 128 x 128, K-contiguous A
+    ("gemm", "NT", 3968, 2048, 512, 0, 0, 1, "", "gemm_ring_kernel<false, false, 2, 4>"),        # 496 tiles
+    ("gemm", "TN", 4096, 2048, 512, 1, 0, 1, "", "gemm_kernelIDF16bLb1ELb1ELi64ELi2ELi4E"),        # transposed A
+    # ring: K-contiguous operands, K % 64 == 0; 64-row tiles up to 128 full tiles and M > 64, 128-row tiles up to 512
+    ("gemm", "NT", 1024, 2048, 512, 0, 0, 1, "", "gemm_ring_kernel<false, false, 1, 4>"),        # 128 tiles
+    ("gemm", "NT", 1024, 2176, 512, 0, 0, 1, "", "gemm_ring_kernel<false, false, 2, 4>"),        # 136
+    ("gemm", "NT", 72, 2048, 2048, 0, 0, 1, "", "gemm_ring_kernel<false, false, 1, 4>"),         # M > 64
+    ("gemm", "NT", 64, 2048, 2048, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb0ELi128ELi2ELi4E"),
+    ("gemm", "NT", 1024, 2048, 520, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb0ELi64ELi1ELi4E"),        # K % 64 != 0
+    # register-staged: 64-row tiles up to 128 full tiles (M > 64), K-step 128 up to 256 tiles with K >= 512, else K-step 64
+    ("gemm", "TN", 1024, 2048, 512, 1, 0, 1, "", "gemm_kernelIDF16bLb1ELb1ELi64ELi1ELi4E"),        # 128 tiles
+    ("gemm", "TN", 1024, 2176, 512, 1, 0, 1, "", "gemm_kernelIDF16bLb1ELb1ELi128ELi2ELi4E"),        # 136
+    ("gemm", "NT", 2048, 2048, 520, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb0ELi128ELi2ELi4E"),        # 256 tiles
+    ("gemm", "NT", 2048, 2176, 520, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),        # 272
+    ("gemm", "NT", 2048, 2048, 504, 0, 0, 1, "", "gemm_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),        # K < 512
+    # ---- multi-problem launches: either side of every threshold, in rule order
+    # 256 x 128 tiles: 128 <= tiles <= 288, < 128 tiles of 256 x 256, shortest K >= 512, M >= 256
+    ("gemm_multi", "NT", 1024, (2048, 2048), (2048, 2048), 0, 0, 1, "", "gemm_sp_multi_kernel<false, false, 6>"),                       # 128 tiles
+    ("gemm_multi", "NT", 1024, (2048, 1920), (2048, 2048), 0, 0, 1, "", "gemm_pk_multi_kernel<false, false, 5>"),                       # 124
+    ("gemm_multi", "TN", 1024, (2048, 2048, 2048, 1792), (1024,) * 4, 1, 0, 1, "", "gemm_sp_multi_kernel<true, true, 6>"),            # 124 tiles of 256 x 256
+    ("gemm_multi", "TN", 1024, (2048,) * 4, (1024,) * 4, 1, 0, 1, "", "gemm_p8_multi_kernel<true, true>"),                         # 128 tiles of 256 x 256
+    ("gemm_multi", "NT", 1024, (2048,) * 4, (1024,) * 4, 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),                         # the same, K-contiguous A
+    ("gemm_multi", "NT", 1024, _H3, (2048, 1024, 448), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),                            # shortest K = 448
+    ("gemm_multi", "NT", 248, (16384,), (1024,), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi128ELi2ELi4E"),                                 # M < 256
+    # 128 x 128 tiles: 96 <= tiles <= 288, < 128 tiles of 256 x 128, shortest K >= 512
+    ("gemm_multi", "NT", 512, (2048, 1024), (2048, 2048), 0, 0, 1, "", "gemm_pk_multi_kernel<false, false, 5>"),                        # 96 tiles
+    ("gemm_multi", "NT", 512, (2048, 896), (2048, 2048), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi1ELi4E"),                         # 92
+    ("gemm_multi", "NT", 512, _H3, (2048, 2048, 448), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),                             # shortest K = 448
+    ("gemm_multi", "NT", 120, (16384,), (1024,), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi1ELi4E"),                                 # M < 128
+    # 256 x 256 tiles: transposed A, >= 128 tiles, shortest K >= 512
+    ("gemm_multi", "TN", 2048, (2048, 2048), (1024, 1024), 1, 0, 1, "", "gemm_p8_multi_kernel<true, true>"),                       # 128 tiles
+    ("gemm_multi", "TN", 2048, (2048, 1792), (1024, 1024), 1, 0, 1, "", "gemm_sp_multi_kernel<true, true, 6>"),                       # 120
+    ("gemm_multi", "TN", 2048, _H3, (448, 448, 448), 1, 0, 1, "", "gemm_multi_kernelIDF16bLb1ELb1ELi64ELi2ELi4E"),                              # K = 448
+    ("gemm_multi", "NT", 2048, _H3, (1024, 1024, 1024), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),                           # K-contiguous A
+    ("gemm_multi", "TN", 2048, _H3, (2048, 2048, 2048), 1, 1, 2, "", "gemm_p8_multi_kernel<true, true>"),                           # split K
+    # register-staged: 64-row tiles up to 128 tiles, K-step 128 up to 256 tiles with shortest K >= 512, else K-step 64
+    ("gemm_multi", "NT", 256, _H3, (520, 520, 520), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi1ELi4E"),                               # 96 tiles
+    ("gemm_multi", "NT", 512, _H3, (520, 520, 520), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi128ELi2ELi4E"),                               # 192
+    ("gemm_multi", "NT", 512, _H3, (504, 504, 504), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),                               # K < 512
+    ("gemm_multi", "NT", 768, _H3, (520, 520, 520), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E"),                               # 288 tiles
+    ("gemm_multi", "NT", 64, _H3, (520, 520, 520), 0, 0, 1, "", "gemm_multi_kernelIDF16bLb0ELb0ELi128ELi2ELi4E"),                                # M = 64
+]
+
+
+def _pin_launch(N, E, row):
+    """Issue the launch a row of _DISPATCH_PIN describes (operands are zeros: only the kernel choice is observed) -> kernel name."""
+    entry, layout, M, Nn, K, f32, atomic, ksplit, flags = row[:9]
+    ta, tb = {"NT": (0, 0), "NN": (0, 1), "TN": (1, 1)}[layout]
+    z = lambda shape, dt=torch.bfloat16: torch.zeros(shape, device="cuda", dtype=dt)
+    if entry == "moco_logits":
+        B, Kq, dim = M, Nn, K
+        qn, queue = z((B, dim)), z((dim, Kq))
+        if flags == "mode1":
+            N.call("moco_logits", 1, qn, queue, B, Kq, dim, 1.0, z((B, (Kq + 63) // 64, 2), torch.float32), None, 0.0, None)
+        else:
+            N.call("moco_logits", 2, qn, queue, B, Kq, dim, 1.0, None, z((B,), torch.float32), 1.0, z((B, Kq)))
+    elif entry in ("gemm", "gemm_dropout"):
+        dt = torch.float32 if "fp32" in flags else torch.bfloat16
+        A, B = z((K, M) if ta else (M, K), dt), z((K, Nn) if tb else (Nn, K), dt)
+        C = z((M, Nn), torch.float32 if (f32 or "fp32" in flags) else torch.bfloat16)
+        bias = z((Nn,), torch.float32) if "bias" in flags else None
+        if entry == "gemm_dropout":
+            N.call("gemm_dropout", ta, tb, M, Nn, K, 1.0, A, A.shape[1], B, B.shape[1], C, Nn, bias, int("relu" in flags), 1234, 0.3,
+                   torch.zeros(1, device="cuda", dtype=torch.int64), 1.0 / 0.7)
+        else:
+            E.gemm(0 if "fp32" in flags else 1, ta, tb, M, Nn, K, A, A.shape[1], B, B.shape[1], C, Nn, bias=bias, relu=int("relu" in flags),
+                   keep=z((M, Nn), torch.uint8) if "keep" in flags else None, ldk=Nn, gate=z((M, Nn)) if "gate" in flags else None, ldg=Nn,
+                   out_f32=f32, atomic=atomic, ksplit=ksplit)
+    else:
+        Ns, Ks = list(Nn), list(K)
+        As = [z((k, M) if ta else (M, k)) for k in Ks]
+        Bs = [z((k, n) if tb else (n, k)) for n, k in zip(Ns, Ks)]
+        if entry == "gemm_multi_sgd":
+            P, Mo = [z((M, n), torch.float32) for n in Ns], [z((M, n), torch.float32) for n in Ns]
+            E.gemm_multi_sgd(ta, tb, M, Ns, Ks, As, [a.shape[1] for a in As], Bs, [b.shape[1] for b in Bs], P, Mo, [z((M, n)) for n in Ns], Ns,
+                             (1e-3, 0.9, 1e-4, 1.0, None))
+        else:
+            Cs = [z((M, n), torch.float32 if f32 else torch.bfloat16) for n in Ns]
+            E.gemm_multi(ta, tb, M, Ns, Ks, As, [a.shape[1] for a in As], Bs, [b.shape[1] for b in Bs], Cs, Ns, out_f32=f32, atomic=atomic,
+                         ksplit=ksplit)
+    torch.cuda.synchronize()
+    return N.last_kernel()
+
+
+def test_gemm_default_dispatch_is_pinned(N):
+    """Which kernel the default dispatch (no AUDIOSSL_GEMM_FORCE / AUDIOSSL_GEMM_OFF) launches for the shapes of the training step, the
+    transformer blocks and one shape on either side of every threshold of the two choice functions.  The expected names were
+    recorded by running this table against a library built from the commit BEFORE the dispatch was rewritten as choose_single /
+    choose_multi (not from the rewritten code): the rewrite, and any later change to the host side, must not move a launch to another kernel
+    unnoticed.  A deliberate change of a rule updates the rows it moves."""
+    import os
+    from src import engine as E
+    assert not any(k in os.environ for k in ("AUDIOSSL_GEMM_FORCE", "AUDIOSSL_GEMM_OFF"))
+    moved = []
+    for row in _DISPATCH_PIN:
+        got = _pin_launch(N, E, row)
+        if got != row[9]:
+            moved.append((row, got))
+    assert not moved, moved
 
 
 def test_gemm_epilogue_large_grid(N):

@@ -1,4 +1,4 @@
-"""Diagnostic (GPU box): time one bf16 GEMM shape under the current environment switches.  usage: gemm_one.py NT 6144 2048 2048"""
+"""Diagnostic (GPU box): time one bf16 GEMM shape under the current environment switches (AUDIOSSL_GEMM_FORCE=<variant>, AUDIOSSL_GEMM_OFF=<variant>[,...]).  usage: gemm_one.py NT 6144 2048 2048"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "audio-ssl_amd"), os.path.join(ROOT, "tools")]

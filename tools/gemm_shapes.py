@@ -1,5 +1,5 @@
-"""Diagnostic (GPU box): time and check every GEMM shape of the DeLoRes-M step under one kernel variant
-(AUDIOSSL_GEMM_RING = 10 * MI + NST, 0 = register-staged kernels only, unset = production dispatch).
+"""Diagnostic (GPU box): time and check every GEMM shape of the DeLoRes-M step under the production dispatch, or with one variant
+forced (AUDIOSSL_GEMM_FORCE=ring64, ...) or some switched off (AUDIOSSL_GEMM_OFF=ring64,ring128: no ring kernels).
 Launches are timed inside a captured graph of back-to-back launches; the result is compared with torch.matmul on the same
 bf16 operands."""
 import os, sys
@@ -55,7 +55,7 @@ def main():
         us = timeit(run)
         tot += us * cnt
         print(f"{mode} {M:5d}x{Nn:5d}x{K:5d} ks={ks} {extra:15s} {us:7.1f} us x{cnt}  {2.0*M*Nn*K/us/1e6:7.1f} TF/s  relerr {err:.1e}" + ("  <-- WRONG" if err > 2e-2 else ""), flush=True)
-    print(f"weighted total {tot:.0f} us/step   (AUDIOSSL_GEMM_RING={os.environ.get('AUDIOSSL_GEMM_RING')})")
+    print(f"weighted total {tot:.0f} us/step   (FORCE={os.environ.get('AUDIOSSL_GEMM_FORCE')}, OFF={os.environ.get('AUDIOSSL_GEMM_OFF')})")
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Diagnostic (GPU box): the twelve multi-problem GEMM launches of the grouped Barlow heads (B = 512: M = 1024 stacked views),
 timed back to back inside a captured graph and checked against torch.matmul on the same bf16 operands.
-Kernel choice follows the production dispatch; AUDIOSSL_GEMM_P6=0 / AUDIOSSL_GEMM_P8=0 in the environment switch the hand-scheduled
+Kernel choice follows the production dispatch; AUDIOSSL_GEMM_OFF=p8,sp6,pk5 in the environment switches the hand-scheduled
 kernels off (run the script twice to compare)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,9 +46,9 @@ def main():
         fl = sum(2.0 * M * n * k for n, k in zip(Ns, Ks))
         tot_us += us * COUNT[name]; tot_fl += fl * COUNT[name]
         print(f"{name}  M={M:5d} N={Ns} K={Ks}: {us:7.1f} us  {fl / us / 1e6:7.1f} TF/s  relerr {err:.1e}"
-              + ("  <-- WRONG" if err > 2e-2 else ""), flush=True)
+              + f"  {N.last_kernel()}" + ("  <-- WRONG" if err > 2e-2 else ""), flush=True)
     print(f"heads GEMM total {tot_us:.0f} us/step, {tot_fl / tot_us / 1e6:.0f} TF/s "
-          f"(P6={os.environ.get('AUDIOSSL_GEMM_P6')}, P8={os.environ.get('AUDIOSSL_GEMM_P8')})")
+          f"(FORCE={os.environ.get('AUDIOSSL_GEMM_FORCE')}, OFF={os.environ.get('AUDIOSSL_GEMM_OFF')})")
 
 
 if __name__ == "__main__":
