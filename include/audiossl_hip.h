@@ -44,6 +44,26 @@ int audiossl_logmel_fwd(const float* wave, float* out, int B, int L, int T, int 
                         const float* win, const float* tw, const float* melw, const int* mel_start, float eps_pow,
                         float eps_log, int apply_log, void* stream);
 
+/* ---- K1b Kaldi fbank front end of the MAST loader: extras/mast_new/mast/dataloader.py:129-130 (kaldi.fbank, htk_compat,
+ * hanning, dither 0), :132-142 (cut / zero-pad to target_length), :187-202 (FrequencyMasking, TimeMasking, (x - mean) / (2 std)),
+ * :105-127 (two-file mix) --------------------------------------------------------------------------------------------------
+ * wave [B][Lmax] f32, lens [B] (NULL: every clip is Lmax long) -> out [B][1][n_mels][T_target] f32, or [B][T_target][n_mels]
+ * when time_major.  Clip b has 1 + (len_b - win_len)/shift frames (0 when len_b < win_len, no centre padding); each frame
+ * loses its mean, is pre-emphasised (y[i] = x[i] - preemph x[i-1], x[-1] = x[0]), multiplied by `win`[win_len] (symmetric
+ * Hann), zero-padded to n_fft = 512 (256 < win_len <= 512) and transformed with `tw` = exp(-2 pi i k/512) as [512][2]; power bins
+ * 0..255 go through `melw` [n_mels][taps] = packed non-zero run of each filterbank row starting at bin mel_start[m]
+ * (taps <= 29, n_mels <= 128) into log(max(., eps_log)).  Frames past the clip's last up to T_target are 0, frames past T_target are
+ * dropped; cells with mel row in [f0,f1) or frame in [t0,t1) of `bands` [B][4] = {f0,f1,t0,t1} (NULL: no masks) become 0; unless
+ * skip_norm every cell, padding and masked ones included, becomes (v - mean) / (2 std).
+ * bands_host (optional) is the caller's HOST copy of `bands`: when given it is checked against [0,n_mels] / [0,T_target] before the
+ * launch.  partner [B] (-1: none) and lam [B] (both or neither): samples are lam w[b] + (1 - lam) w[partner[b]], the partner
+ * zero-padded or cut to len_b.  clip_mean [B] (optional scratch, only with partner): a first launch fills it with the whole-clip
+ * means and the mix uses w - mean (dataloader.py:108-109; without a mix the per-frame mean removal cancels it exactly). */
+int audiossl_fbank_fwd(const float* wave, const int* lens, const int* partner, const float* lam, float* clip_mean,
+                       const int* bands, const int* bands_host, float* out, int B, int Lmax, int win_len, int shift, int n_fft, int n_mels,
+                       int taps, int T_target, const float* win, const float* tw, const float* melw, const int* mel_start,
+                       float preemph, float eps_log, float mean, float std, int skip_norm, int time_major, void* stream);
+
 /* ---- K2 RunningNorm: src/augmentations/augmentations.py:215-282 ----------------------------------------
  * clip_moments: mom[c] = {sum x, sum x^2} (fp64) of clip c over n = F*T elements.
  * runnorm_scan: sequential recurrence over the batch; state_i = {n_seen, max_update}, state_f = {mu, s2};
