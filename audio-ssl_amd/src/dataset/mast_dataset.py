@@ -5,7 +5,7 @@ optional two-file mix - one `audiossl_fbank_fwd` call per batch (one kernel; wit
   kaldi_mel_banks / kaldi_window   the tables of torchaudio.compliance.kaldi (its operation order; the bank in float64, rounded once)
   plan_masks                       torchaudio's `mask_along_axis` draws from torch's global CPU generator, per clip
   plan_mix                         `__getitem__`'s mix draws (python `random`, numpy's global generator)
-  MastFrontEnd(audio_conf)         waves -> [B, 1, F, T] network input on the device
+  MastFrontEnd(audio_conf)         waves (or a right-padded `ingest.PcmBatch`) -> [B, 1, F, T] network input on the device
   make_features                    `run_mvit.py`'s function with its built-in AudioSet statistics
   norm_stats                       `get_norm_stats.py`
 
@@ -206,7 +206,15 @@ class MastFrontEnd:
         self.last_plan = None
 
     def __call__(self, waves, lens=None, time_major=False):
-        waves, lens = _batch(waves, lens)
+        """waves: [B, L] tensor, a list of 1-D clips, or a `PcmBatch` packed with align=1 (its windows are converted on the device,
+        `lens` are the batch's frame counts and Lmax its unit)."""
+        from src.dataset.ingest import PcmBatch, pcm_window
+        if isinstance(waves, PcmBatch):
+            if waves.align != 1:
+                raise ValueError("the fbank front end takes right-padded clips: PcmBatch.pack(..., align=1)")
+            waves, lens = pcm_window(waves), waves.lens
+        else:
+            waves, lens = _batch(waves, lens)
         B = waves.shape[0]
         partner, lam, bands = plan_batch(B, self.melbins, self.target_length, self.freqm, self.timem, self.mixup)
         self.last_plan = (partner, lam, bands)               # lam weighs the labels (dataloader.py:170-174)

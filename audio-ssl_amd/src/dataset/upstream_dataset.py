@@ -6,8 +6,11 @@ only decodes and crops (the window start is drawn with the reference's generator
 python `random` stream), and `UpstreamFrontEnd` turns a whole [B, L] waveform batch into the two [B,1,64,T] views
 with three fused launches (log-mel, normalise, views).
 Decoding: the reference uses librosa.core.load (audioread/soundfile + resampy); neither is in the image, so WAV
-files are read with scipy.io.wavfile (and .npy arrays directly) and resampled with scipy.signal.resample_poly -
-audio ingest is a "next" row of SURVEY 8f, not part of the parity-checked hot path.
+files are read with scipy.io.wavfile (and .npy arrays directly) and resampled on the GPU with the windowed-sinc kernel of
+`src/dataset/ingest.py` (resampy's kaiser_best restated, parity unpinned).
+`pcm=True` (config key `run.pcm_upload`) ships the windows in the files' own sample formats: the collate returns a `PcmBatch`
+(one packed upload, half the bytes for 16-bit audio) and the front end converts it on the GPU (`ingest.pcm_window`) into the
+same float32 batch, bit for bit.
 """
 import numpy as np
 import pandas as pd
@@ -22,12 +25,20 @@ from src.utils import MelSpectrogramLibrosa, extract_log_mel_spectrogram, extrac
 AUDIO_SR = 16000
 
 
-def load_audio(path, sr=AUDIO_SR):
+def load_audio(path, sr=AUDIO_SR, raw=False):
     """-> float32 mono numpy array at `sr`: host decode (`ingest.decode`), then the windowed-sinc resampler on the GPU
     (`ingest.resample`, resampy kaiser_best as librosa.core.load uses it).  Inside a DataLoader worker process (no GPU context
-    there) the clip is returned at its native rate wrapped in `NativeRate`; the main-process collate resamples it."""
+    there) the clip is returned at its native rate wrapped in `NativeRate`; the main-process collate resamples it.
+    raw: a file already at `sr` is returned as a `PcmClip` in its own sample format (`ingest.decode_raw`); other rates go through
+    the resampler as float32, as without it."""
     from src.dataset import ingest
-    data, rate = ingest.decode(path)
+    if raw:
+        clip = ingest.decode_raw(path)
+        if clip.rate == sr:
+            return clip
+        data, rate = clip.to_float(), clip.rate
+    else:
+        data, rate = ingest.decode(path)
     if rate == sr:
         return data
     import torch.utils.data as tud
@@ -44,7 +55,7 @@ class NativeRate:
 
 
 class UpstreamFrontEnd:
-    """waveforms [B, L] (device) -> (img_1, img_2), each [B, 1, n_mels, T] float32, entirely on the GPU."""
+    """waveforms [B, L] (device) or a `PcmBatch` -> (img_1, img_2), each [B, 1, n_mels, T] float32, entirely on the GPU."""
 
     def __init__(self, config, tfms):
         self.config = config
@@ -61,7 +72,9 @@ class UpstreamFrontEnd:
     @torch.no_grad()
     def log_mel(self, waves):
         """[B, L] device waveforms -> [B, n_mels, T] log-mel; `normalization: l2` first scales every clip to unit L2 norm
-        (`F.normalize(waveform, dim=-1, p=2)`, src/dataset/upstream_dataset.py:61-62 of the reference) - one wave per clip."""
+        (`F.normalize(waveform, dim=-1, p=2)`, src/dataset/upstream_dataset.py:61-62 of the reference) - one wave per clip.
+        A `PcmBatch` is converted to that waveform tensor first."""
+        waves = _waveforms(waves)
         if self.l2:
             waves = waves.float().contiguous()
             out = torch.empty_like(waves)
@@ -103,8 +116,19 @@ class UpstreamFrontEnd:
         return views
 
 
+def _waveforms(waves):
+    """A `PcmBatch` (host or device) -> its [B, unit] float32 device tensor, centre padded; tensors pass through."""
+    from src.dataset.ingest import PcmBatch, pcm_window
+    if not isinstance(waves, PcmBatch):
+        return waves
+    if waves.align != 0:
+        raise ValueError("the log-mel front ends take centre-padded windows: PcmBatch.pack(..., align=0)")
+    return pcm_window(waves)
+
+
 class BaseDataset(Dataset):
-    def __init__(self, config, args, data_csv, tfms, per_sample=False):
+    def __init__(self, config, args, data_csv, tfms, per_sample=False, pcm=False):
+        self.pcm = pcm
         self.config = config
         self.tfms = tfms
         self.length = self.config["pretrain"]["input"]["length_wave"]
@@ -122,9 +146,13 @@ class BaseDataset(Dataset):
         return int(self.length * 16000)
 
     def __getitem__(self, idx):
-        wave = load_audio(self.data["files"][idx], self.sampling_rate)
+        wave = load_audio(self.data["files"][idx], self.sampling_rate, raw=self.pcm)
         if isinstance(wave, NativeRate):
             return wave                      # resampled on the GPU by the main-process collate
+        if not isinstance(wave, np.ndarray):
+            if not self.per_sample:
+                return wave                  # a PcmClip: packed in its own sample format at collate time
+            wave = wave.to_float()
         wave = torch.from_numpy(wave)
         if not self.per_sample:
             return wave                      # cropped at collate time, with the draws in the reference's order
@@ -144,10 +172,11 @@ class WindowCollate:
 
     The python `random` stream is consumed exactly as the reference's sequential loader would (per clip: the window
     start, then that clip's view parameters), so crops and augmentation indices are bit-identical to a reference run
-    with `num_workers=0`."""
+    with `num_workers=0`.  pcm=True: the same draws and plan, and the windows leave as a `PcmBatch` (`PcmClip`s in their own
+    sample formats, resampled clips as float32) in place of the zero-padded float32 tensor."""
 
-    def __init__(self, tfms, unit_length, n_mels, hop=160):
-        self.tfms, self.unit, self.n_mels, self.hop = tfms, unit_length, n_mels, hop
+    def __init__(self, tfms, unit_length, n_mels, hop=160, pcm=False):
+        self.tfms, self.unit, self.n_mels, self.hop, self.pcm = tfms, unit_length, n_mels, hop, pcm
 
     def __call__(self, waves):
         from src.dataset import ingest
@@ -158,6 +187,8 @@ class WindowCollate:
         self.tfms._ensure_ring(B)
         plan = self.tfms.plan(B, self.n_mels, T, lens=lens, unit=self.unit)
         starts = self.tfms.last_starts
+        if self.pcm:
+            return ingest.PcmBatch.pack(waves, starts, self.unit), plan
         out = torch.zeros(B, self.unit, dtype=torch.float32)
         for b, w in enumerate(waves):
             n = len(w)
@@ -170,8 +201,9 @@ class WindowCollate:
 
 
 class BaselineDataModule:
-    def __init__(self, config, args, tfms, data_csv='./', batch_size=8, num_workers=8):
+    def __init__(self, config, args, tfms, data_csv='./', batch_size=8, num_workers=8, pcm=False):
         self.config = config
+        self.pcm = pcm
         self.args = args
         self.data_dir_train = data_csv
         self.batch_size = batch_size
@@ -183,12 +215,12 @@ class BaselineDataModule:
 
     def setup(self, stage=None):
         if stage == 'fit' or stage is None:
-            self.train_dataset = BaseDataset(self.config, self.args, self.data_dir_train, self.transformation)
+            self.train_dataset = BaseDataset(self.config, self.args, self.data_dir_train, self.transformation, pcm=self.pcm)
             self.dataset_sizes['train'] = len(self.train_dataset)
 
     def train_dataloader(self, sampler=None):
         unit = self.train_dataset.unit_length
-        collate = WindowCollate(self.transformation, unit, self.config["pretrain"]["input"]["n_mels"])
+        collate = WindowCollate(self.transformation, unit, self.config["pretrain"]["input"]["n_mels"], pcm=self.pcm)
         # decoding / resampling runs in `run.num_dataloader_workers` worker processes (they return the raw clips of a batch);
         # cropping + augmentation planning is stateful (ONE sequential random stream, as a reference run with num_workers=0
         # consumes it) and stays in the main process, applied to each batch as it arrives

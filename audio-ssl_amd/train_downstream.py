@@ -27,7 +27,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
-from src.dataset.downstream_dataset import DownstreamDataset, DownstreamFrontEnd  # noqa: E402
+from src.dataset.downstream_dataset import DownstreamDataset, DownstreamFrontEnd, PcmCollate  # noqa: E402
 from src.downstream.downstream_encoder import DownstreamEncoder  # noqa: E402
 from src.flat import FlatGroup  # noqa: E402
 from src.optim import HipAdamW  # noqa: E402
@@ -124,12 +124,15 @@ def main(args):
     stats_file = open(exp_root / "downstream_stats.txt", "a", buffering=1) if rank == 0 else None
     assert config["run"]["batch_size"] % world == 0
     per_device_batch_size = config["run"]["batch_size"] // world
-    train_dataset = DownstreamDataset(args, config, split="train")
-    test_dataset = DownstreamDataset(args, config, split="test", labels_dict=train_dataset.labels_dict)
+    pcm = bool(config["run"].get("pcm_upload", False))      # ship the windows in the files' sample formats, convert on the GPU
+    collate = PcmCollate(int(config["run"]["duration"] * 16000)) if pcm else None
+    train_dataset = DownstreamDataset(args, config, split="train", pcm=pcm)
+    test_dataset = DownstreamDataset(args, config, split="test", labels_dict=train_dataset.labels_dict, pcm=pcm)
     sampler = torch.utils.data.distributed.DistributedSampler(train_dataset, world, rank, shuffle=True, seed=1)
     train_loader = torch.utils.data.DataLoader(train_dataset, batch_size=per_device_batch_size, pin_memory=True, sampler=sampler,
-                                               num_workers=0)
-    test_loader = torch.utils.data.DataLoader(test_dataset, batch_size=per_device_batch_size, pin_memory=True, num_workers=0)
+                                               num_workers=0, collate_fn=collate)
+    test_loader = torch.utils.data.DataLoader(test_dataset, batch_size=per_device_batch_size, pin_memory=True, num_workers=0,
+                                              collate_fn=collate)
     if args.encoder is not None:
         config["downstream"]["base_encoder"]["type"] = args.encoder
     base_encoder = getattr(importlib.import_module("src.encoder"), config["downstream"]["base_encoder"]["type"])

@@ -170,7 +170,7 @@ def main(args):
         torch.manual_seed(args.seed)
     tfms = AugmentationModule(config, len(pd.read_csv(args.input)), max_batch=config["run"]["batch_size"])
     dm = BaselineDataModule(config, args, tfms, data_csv=args.input, num_workers=config["run"]["num_dataloader_workers"],
-                            batch_size=config["run"]["batch_size"])
+                            batch_size=config["run"]["batch_size"], pcm=bool(config["run"].get("pcm_upload", False)))
     expert = getattr(importlib.import_module(f'src.upstream.{args.upstream}.upstream_expert'), 'Upstream_Expert')
     base_encoder = getattr(importlib.import_module('src.encoder'), config["pretrain"]["base_encoder"]["type"])
     model = expert(config, base_encoder=base_encoder, datamodule=dm)

@@ -101,6 +101,21 @@ int audiossl_resample_sinc(const float* x, float* y, int clips, int n_orig, int 
                            const int* off_r, const double* eta_l, const double* eta_r, const double* win, const double* delta,
                            int nwin, int index_step, void* stream);
 
+/* ---- f3 packed PCM batches: the sample conversion and channel mean of `librosa.core.load` (src/dataset/upstream_dataset.py:55) and
+ * `torchaudio.load` (extras/mast_new/mast/dataloader.py:101), and the window of src/utils/utils.py:166-182, moved behind the upload.
+ * pcm = pcm_bytes bytes of interleaved frames in the files' own sample formats; tab [B][4] int64 = {byte offset of the clip's first
+ * frame in pcm, frames n, channels C, format (0 u8, 1 s16, 2 s32 - 24-bit files left-justified -, 3 f32)} -> out [B][unit] f32.
+ * A sample becomes (x - 128) / 128, x / 2^15, float(x) / 2^31 or itself; a frame is its channels added in float32 in the order of
+ * numpy's mean(axis=1) (first to last; C = 8: ((c0+c1)+(c2+c3))+((c4+c5)+(c6+c7))) and divided by C.  align 0: (unit - n) / 2 zeros,
+ * the n frames, zeros (the window's centre padding); align 1: the frames first (the fbank batch).  n = 0 gives a row of zeros; the
+ * host cuts longer clips at their drawn start, so n <= unit.
+ * tab_host (required) is the caller's HOST copy of tab; every row is checked before the launch: format in 0..3, C in 1..8,
+ * 0 <= n <= unit, offset a multiple of the sample size, offset + n C size <= pcm_bytes (EINVAL, as for B > 65535 or align not 0 / 1).
+ * pcm and out 16-byte aligned and pcm_bytes a multiple of 16 (EALIGN): the mono s16 rows are read in aligned 16-byte chunks that
+ * touch the clip, which then never leave [pcm, pcm + pcm_bytes).  16-byte stores when unit % 4 == 0. */
+int audiossl_pcm_window(const void* pcm, long pcm_bytes, const long long* tab, const long long* tab_host, float* out, int B,
+                        int unit, int align, void* stream);
+
 /* ---- a10 Kmix: src/augmentations/augmentations.py:119-189 (cluster-guided mixup of the finished views) -------------------
  * kmix_cluster: cluster[v] = first argmin_c ||mean_T(views[v]) - centroids[c]|| (centroids [K][F] with unit rows: what
  *   `get_index` computes for the view itself and, once it sits in the memory bank, for the bank entry).
