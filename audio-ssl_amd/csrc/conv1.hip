@@ -5,7 +5,8 @@
 // A 3x3 convolution of a single-channel image is linear in 9 shifted copies x_tap of that image, so the
 // batch statistics of every output channel follow from the 9 first and 45 second moments of the taps:
 //   mean_c = w_c . S1 / n + b_c,   var_c = w_c^T Cov w_c            (moments kernel + finalize, fp64)
-// and the forward is ONE pass that recomputes the conv per pooled pixel and writes only the pooled map.
+// and the forward is ONE pass that recomputes the conv per pooled pixel and writes only the pooled map.  In bf16 training the
+// finalize is the prologue of that pass (conv1_fwd_train): two launches per view, moments and forward.
 // The backward never needs dX (the input is data), and BN's correction terms are again linear in the
 // same moments:
 //   dW_c,tap = gamma rstd [ G_c,tap - dbeta_c/n S1_tap - dgamma_c/n * rstd (w_c . S2[:,tap] + (b_c-mean_c) S1_tap) ]
@@ -16,134 +17,229 @@
 
 namespace {
 
-constexpr int NTAP = 9, NMOM = 9 + 45;
+constexpr int NMOM = 9 + 45;
 constexpr int MOM_REPL = 16;  // replicas of the moment accumulator (`mom` scratch = MOM_REPL * 54 doubles)
 
 __device__ __forceinline__ int tri(int a, int b) {   // index of pair (a<=b) in the packed upper triangle
     return a * 9 - a * (a - 1) / 2 + (b - a);
 }
 
-// One workgroup per (image, chunk of MOM_TC time columns): the chunk (+ halo, zero outside the image) is staged in LDS once,
-// each thread then walks pixels p = tid, tid+256, ... of the chunk reading its 9 taps from LDS (lanes run along time:
-// conflict-free), 54 FMAs per pixel.  (A flat grid-stride loop with 9 global loads per pixel was latency-bound: 52 us at
-// N = 512 for 13 MB of input.)
-constexpr int MOM_TC = 128;
-__global__ __launch_bounds__(256) void conv1_moments_kernel(const float* __restrict__ img, double* __restrict__ mom,
-                                                            int N, int F, int T, int nchunk, int tcw) {
-    extern __shared__ float tile[];                               // [(F+2)][tc+2]
-    __shared__ float sh[4][NMOM];
-    const int n = blockIdx.x / nchunk, t0 = (blockIdx.x - n * nchunk) * tcw;
-    const int tc = min(tcw, T - t0), ld = tc + 2;
-    const float* im = img + (long)n * F * T;
-    {
-        // eight independent loads in flight per thread and pass (a one-load-per-iteration loop with a division per element
-        // spent ~40 us of this kernel waiting); (row, column) of element i advance incrementally: i += 256
-        const int total = (F + 2) * ld, dr = 256 / ld, dc = 256 - dr * ld;
-        int r = threadIdx.x / ld, cidx = threadIdx.x - r * ld;
-        for (int i0 = threadIdx.x; i0 < total; i0 += 8 * 256) {
-            float v[8];
-            int rr = r, cc = cidx;
+// Moment slot of one view (AUDIOSSL_CONV1_MOM_SLOT doubles): [0..53] the 54 totals, then MOM_REPL replica sets of 54.  The moments
+// kernel adds into the replicas; whoever finalizes folds them in replica order and leaves the totals in [0..53] (the backward
+// reads those).  The totals sit in front of the replicas, not on top of replica 0, because in the fused stem forward every
+// workgroup folds the replicas while workgroup 0 writes the totals.
+constexpr int MOM_SLOT = (1 + MOM_REPL) * NMOM;
+
+// Tap moments of up to two views in one launch.  Items are (image, band of MOM_BAND rows, chunk of MOM_TC time columns); a
+// workgroup belongs to one view (blockIdx.y) and walks items blockIdx.x, + gridDim.x, ...: the item (+ halo, zero outside the
+// image) is staged in LDS, the NEXT item's elements are already on their way into registers while the products of this one are
+// accumulated (lanes along time: conflict-free LDS reads), and the cross-lane reduction and the 54 fp64 atomics happen once per
+// workgroup, not once per image.  (One workgroup per image that staged, computed, reduced and added strictly in that order was
+// bound by that serial chain: 44 us per view in the step for 13 MB and 54 FMAs per pixel; a flat grid-stride loop with 9 global
+// loads per pixel: 52 us.)  fp32 accumulation stays inside one lane's run, which the launcher bounds at 256 pixels.
+constexpr int MOM_BAND = 16, MOM_TC = 128;
+constexpr int MOM_TILE = (MOM_BAND + 2) * (MOM_TC + 2);
+constexpr int MOM_PRE = (MOM_TILE + 255) / 256;                   // staged elements per thread and item
+constexpr int MOM_RUN = 32;                                       // items per workgroup at most: 32 * (16 * 128 / 256) = 256 pixels per lane
+
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+// index of tap pair j (taps 2j, 2j + 1; tap 9 is the constant 1) in row a of the packed accumulators: rows hold 5,5,4,4,3,3,2,2,1 pairs
+constexpr int MOM_NPK = 29;
+__device__ __forceinline__ constexpr int mom_pk(int a, int j) {
+    int base = 0;
+    for (int r = 0; r < a; ++r) base += 5 - r / 2;
+    return base + (j - a / 2);
+}
+
+struct MomItem { const float* im; int f0, rows, t0, tc; };
+__device__ __forceinline__ MomItem mom_item(const float* __restrict__ img, int item, int F, int T, int nband, int nchunk) {
+    const int per = nband * nchunk, n = item / per, rem = item - n * per, b = rem / nchunk, ch = rem - b * nchunk;
+    MomItem it;
+    it.im = img + (long)n * F * T;
+    it.f0 = b * MOM_BAND; it.rows = min(MOM_BAND, F - it.f0);
+    it.t0 = ch * MOM_TC;  it.tc = min(MOM_TC, T - it.t0);
+    return it;
+}
+// element i of the staged tile [(rows + 2)][tc + 2] is image element (f0 - 1 + i / ld, t0 - 1 + i % ld).  The quotient comes from
+// one multiplication: i < 2,560 and ld <= 130, so (i + 0.5) / ld is at least 0.5 / 130 away from an integer - a thousand times
+// the rounding error of the product.
+struct MomRegs {
+    float v[MOM_PRE];
+    __device__ __forceinline__ void fetch(const MomItem& it, int F, int T) {
+        const int ld = it.tc + 2, total = (it.rows + 2) * ld;
+        const float inv = 1.f / (float)ld;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int f = rr - 1, t = t0 + cc - 1;
-                v[k] = (i0 + k * 256 < total && f >= 0 && f < F && t >= 0 && t < T) ? im[f * T + t] : 0.f;
-                cc += dc; rr += dr;
-                if (cc >= ld) { cc -= ld; ++rr; }
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (i0 + k * 256 < total) tile[i0 + k * 256] = v[k];
-            r = rr; cidx = cc;
+        for (int k = 0; k < MOM_PRE; ++k) {
+            const int i = threadIdx.x + k * 256;
+            const int r = (int)(((float)i + 0.5f) * inv), f = it.f0 - 1 + r, t = it.t0 - 1 + (i - r * ld);
+            v[k] = (i < total && f >= 0 && f < F && t >= 0 && t < T) ? it.im[f * T + t] : 0.f;
         }
     }
-    __syncthreads();
-    float acc[NMOM];
+    __device__ __forceinline__ void put(float* tile, const MomItem& it) const {
+        const int total = (it.rows + 2) * (it.tc + 2);
 #pragma unroll
-    for (int i = 0; i < NMOM; ++i) acc[i] = 0.f;
-    const int df = 256 / tc, dt = 256 - df * tc;                  // p += 256  ==  (f, t) += (df, dt) with carry
-    int f = threadIdx.x / tc, t = threadIdx.x - f * tc;
-    for (; f < F;) {
-        const float* c = tile + f * ld + t;                       // top-left tap of pixel (f, t)
-        float x[NTAP];
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) x[kh * 3 + kw] = c[kh * ld + kw];
-#pragma unroll
-        for (int a = 0; a < 9; ++a) {
-            acc[a] += x[a];
-#pragma unroll
-            for (int b = 0; b < 9; ++b)                           // (a <= b) pairs; the index is a constant after unrolling - a running
-                if (b >= a) acc[9 + tri(a, b)] += x[a] * x[b];    // counter (acc[q++]) left the array in scratch memory: 46 MB of traffic
+        for (int k = 0; k < MOM_PRE; ++k) {
+            const int i = threadIdx.x + k * 256;
+            if (i < total) tile[i] = v[k];
         }
-        t += dt; f += df;
-        if (t >= tc) { t -= tc; ++f; }
+    }
+};
+
+// Sums over the wave of 64 values per lane: lane l ends with the sum of v[l] in v[0].  Each step halves the values a lane
+// holds - it keeps one half and hands the other to the lane `h` away - so the whole transposition is 63 exchanges, not the
+// 54 x 6 of one butterfly per value.
+template <int H>
+__device__ __forceinline__ void wave_transpose_sum(float (&v)[64], int lane) {
+    const bool up = (lane & H) != 0;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {                                 // (constant indices: a loop over H left the array in scratch memory)
+        const float send = up ? v[k] : v[k + H], keep = up ? v[k + H] : v[k];
+        v[k] = keep + __shfl_xor(send, H, 64);
+    }
+    if constexpr (H > 1) wave_transpose_sum<H / 2>(v, lane);
+}
+
+__global__ __launch_bounds__(256, 4) void conv1_moments_kernel(const float* __restrict__ img_a, const float* __restrict__ img_b,
+                                                               double* __restrict__ rep_a, double* __restrict__ rep_b,
+                                                               int N, int F, int T, int nband, int nchunk) {
+    __shared__ float tile[MOM_TILE];
+    __shared__ float sh[4][64];
+    const float* __restrict__ img = blockIdx.y ? img_b : img_a;
+    double* __restrict__ rep = blockIdx.y ? rep_b : rep_a;
+    const int items = N * nband * nchunk;
+    // The taps are held as five aligned pairs (x0,x1) ... (x8, 1): row a of the moment matrix is x_a times the pairs from a / 2 on,
+    // one packed FMA per pair - 29 per pixel for the 45 second moments and, through the constant 1, the 9 first moments (54 + 9
+    // scalar operations otherwise; this kernel is bound by VALU issue and shares the CUs with the front end's log-mel).  Rows with
+    // odd a carry one redundant element (a, a - 1).
+    f32x2 acc2[MOM_NPK];
+#pragma unroll
+    for (int i = 0; i < MOM_NPK; ++i) acc2[i] = f32x2{0.f, 0.f};
+    MomRegs pre;
+    MomItem cur = {}, nx = {};
+    int item = blockIdx.x;
+    if (item < items) { cur = mom_item(img, item, F, T, nband, nchunk); pre.fetch(cur, F, T); }
+    while (item < items) {
+        pre.put(tile, cur);
+        __syncthreads();
+        const int nxt = item + gridDim.x;
+        if (nxt < items) { nx = mom_item(img, nxt, F, T, nband, nchunk); pre.fetch(nx, F, T); }
+        const int ld = cur.tc + 2, npix = cur.rows * cur.tc;
+        const float inv = 1.f / (float)cur.tc;
+        for (int p = threadIdx.x; p < npix; p += 256) {
+            const int f = (int)(((float)p + 0.5f) * inv), t = p - f * cur.tc;
+            const float* c = tile + f * ld + t;                   // top-left tap of pixel (f0 + f, t0 + t)
+            float x[10];
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) x[kh * 3 + kw] = c[kh * ld + kw];
+            x[9] = 1.f;
+#pragma unroll
+            for (int a = 0; a < 9; ++a) {
+                const f32x2 xa = {x[a], x[a]};
+#pragma unroll
+                for (int j = a / 2; j < 5; ++j)                   // (constant indices after unrolling: the array stays in registers)
+                    acc2[mom_pk(a, j)] = __builtin_elementwise_fma(xa, f32x2{x[2 * j], x[2 * j + 1]}, acc2[mom_pk(a, j)]);
+            }
+        }
+        __syncthreads();
+        item = nxt; cur = nx;
+    }
+    float acc[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int a = 0; a < 9; ++a) {
+        acc[a] = acc2[mom_pk(a, 4)][1];                           // x_a * 1
+#pragma unroll
+        for (int b = a; b < 9; ++b) acc[9 + tri(a, b)] = acc2[mom_pk(a, b / 2)][b & 1];
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NMOM; ++i) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) sh[w][i] = v;
-    }
+    wave_transpose_sum<32>(acc, lane);
+    sh[w][lane] = acc[0];
     __syncthreads();
     if (threadIdx.x < NMOM) {
         const double v = (double)sh[0][threadIdx.x] + (double)sh[1][threadIdx.x] + (double)sh[2][threadIdx.x] +
                          (double)sh[3][threadIdx.x];
-        atomicAdd(&mom[(blockIdx.x & (MOM_REPL - 1)) * NMOM + threadIdx.x], v);     // replicated: same-address atomics serialise
+        atomicAdd(&rep[(blockIdx.x & (MOM_REPL - 1)) * NMOM + threadIdx.x], v);       // replicated: same-address atomics serialise
     }
 }
 
-// 576 threads = (channel, tap a): the 81 covariances once per workgroup, per thread the row sum_b w_b cov(a, b), then the 9 rows of
-// a channel folded in tap order by its first thread.  (One thread per channel walking all 81 products after a serial fold of the
-// replicas: 9 us at the head of both encoder chains.)
-__global__ __launch_bounds__(576) void conv1_finalize_kernel(double* __restrict__ momr, const float* __restrict__ w,
-                                      const float* __restrict__ bias, const float* __restrict__ gamma,
-                                      const float* __restrict__ beta, float* running_mean, float* running_var,
-                                      float momentum, float eps, double count, float* scale, float* shift,
-                                      float* save_mean, float* save_rstd, int repl) {
-    __shared__ double tot[NMOM];
-    __shared__ double cov[81];
-    __shared__ double rowv[64][9], rowm[64][9];
-    const int i = threadIdx.x;
-    // fold the replicas into mom[0..53] (kept for the backward), then every channel reads the totals
-    if (i < NMOM) {
+// BatchNorm scale / shift / mean / rstd of the 64 stem channels from the tap moments, by the NT threads of one workgroup: fold
+// the `repl` replica sets at `rep` in replica order (totals also to tot_out[0..53] when it is given), the 81 covariances, per
+// (channel, tap a) the row sum_b w_b cov(a, b), then the 9 rows of a channel folded in tap order.  ONE definition for the
+// stand-alone finalize kernel and the prologue of the fused stem forward: the two give the same bits from the same totals.
+// Results: L.sc / L.sh always; the global vectors and the running buffers only where `publish`.
+struct StemBnLds {
+    double tot[NMOM], cov[81], rowv[64 * 9];
+    float sc[64], sh[64];
+};
+struct StemBn {
+    double* slot;                                                 // fused forward only: the view's moment slot
+    const float *gamma, *beta;
+    float *running_mean, *running_var;
+    float momentum, eps;
+    double count;
+    float *scale, *shift, *save_mean, *save_rstd;
+};
+template <int NT>
+__device__ __forceinline__ void stem_bn_finalize(StemBnLds& L, const double* rep, int repl, double* tot_out,
+                                                 const float* __restrict__ w, const float* __restrict__ bias, const StemBn& bn,
+                                                 bool publish) {
+    const double count = bn.count;
+    for (int i = threadIdx.x; i < NMOM; i += NT) {
         double t = 0.0;
-        for (int r = 0; r < repl; ++r) t += momr[r * NMOM + i];
-        tot[i] = t;
+        for (int r = 0; r < repl; ++r) t += rep[r * NMOM + i];
+        L.tot[i] = t;
     }
     __syncthreads();
-    if (i < NMOM) momr[i] = tot[i];
-    if (i < 81) {
+    if (tot_out)
+        for (int i = threadIdx.x; i < NMOM; i += NT) tot_out[i] = L.tot[i];
+    for (int i = threadIdx.x; i < 81; i += NT) {
         const int a = i / 9, bb = i - a * 9;
-        const double s2 = tot[9 + (a <= bb ? tri(a, bb) : tri(bb, a))] / count;
-        cov[i] = s2 - (tot[a] / count) * (tot[bb] / count);
+        const double s2 = L.tot[9 + (a <= bb ? tri(a, bb) : tri(bb, a))] / count;
+        L.cov[i] = s2 - (L.tot[a] / count) * (L.tot[bb] / count);
     }
     __syncthreads();
-    const int c = i / 9, a = i - (i / 9) * 9;
-    if (i < 576) {
+    for (int i = threadIdx.x; i < 576; i += NT) {
+        const int c = i / 9, a = i - c * 9;
         double r = 0.0;
-        for (int bb = 0; bb < 9; ++bb) r += (double)w[c * 9 + bb] * cov[a * 9 + bb];
-        rowv[c][a] = (double)w[c * 9 + a] * r;
-        rowm[c][a] = (double)w[c * 9 + a] * tot[a];
+        for (int bb = 0; bb < 9; ++bb) r += (double)w[c * 9 + bb] * L.cov[a * 9 + bb];
+        L.rowv[i] = (double)w[c * 9 + a] * r;
     }
     __syncthreads();
-    if (i < 576 && a == 0) {
+    for (int c = threadIdx.x; c < 64; c += NT) {
         double mean = 0.0, var = 0.0;
-        for (int k = 0; k < 9; ++k) { mean += rowm[c][k]; var += rowv[c][k]; }
+        {
+#pragma clang fp contract(off)                                    // w_k * S1_k is rounded before it is added (it used to pass through LDS)
+            for (int k = 0; k < 9; ++k) { mean += (double)w[c * 9 + k] * L.tot[k]; var += L.rowv[c * 9 + k]; }
+        }
         mean = mean / count;
         var = var < 0.0 ? 0.0 : var;
         mean += (double)bias[c];
-        const double rstd = 1.0 / sqrt(var + (double)eps);
-        const float sc = (float)((double)gamma[c] * rstd);
-        scale[c] = sc;
-        shift[c] = (float)((double)beta[c] - mean * (double)gamma[c] * rstd);
-        save_mean[c] = (float)mean;
-        save_rstd[c] = (float)rstd;
-        if (running_mean) {
-            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(var * count / (count - 1.0));
+        const double rstd = 1.0 / sqrt(var + (double)bn.eps);
+        const float sc = (float)((double)bn.gamma[c] * rstd);
+        const float sh = (float)((double)bn.beta[c] - mean * (double)bn.gamma[c] * rstd);
+        L.sc[c] = sc;
+        L.sh[c] = sh;
+        if (publish) {
+            bn.scale[c] = sc;
+            bn.shift[c] = sh;
+            bn.save_mean[c] = (float)mean;
+            bn.save_rstd[c] = (float)rstd;
+            if (bn.running_mean) {
+                bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * (float)mean;
+                bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * (float)(var * count / (count - 1.0));
+            }
         }
     }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(576) void conv1_finalize_kernel(double* __restrict__ momr, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, StemBn bn, int repl) {
+    __shared__ StemBnLds L;
+    stem_bn_finalize<576>(L, momr, repl, momr, w, bias, bn, true);
 }
 
 // Stage the 4 time columns x (F+2) mel rows an (n, tp) item needs: patch[f+1][k] = img[n][f][2tp-1+k].
@@ -340,10 +436,14 @@ __device__ __forceinline__ Vec8<bf16> stem_weights(const float* w, int c, int ha
     return b;
 }
 
+// TRAIN: scale / shift are not read but derived in the prologue, by every workgroup, from the view's moment slot (stem_bn_finalize
+// on the LDS that the patch and the staging tile use afterwards); workgroup 0 publishes them with mean / rstd, the running
+// buffers and the folded totals - the 576-thread finalize launch between the moments and this kernel is gone.
+template <bool TRAIN>
 __global__ __launch_bounds__(256) void conv1_fwd_mfma_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                              const float* __restrict__ bias, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, bf16* __restrict__ out,
-                                                             float* __restrict__ xl, int XS, int N, int F, int T) {
+                                                             float* __restrict__ xl, int XS, int N, int F, int T, StemBn bn) {
     extern __shared__ __attribute__((aligned(16))) float patch[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const int To = T / 2, Fo = F / 2;
@@ -352,11 +452,19 @@ __global__ __launch_bounds__(256) void conv1_fwd_mfma_kernel(const float* __rest
     bf16* const stage = reinterpret_cast<bf16*>(patch + (((F + 2) * 4 + 3) & ~3));
     Vec8<bf16> wb[2];
     float b[2], sc[2], sh[2];
+    if (TRAIN) {
+        StemBnLds& L = *reinterpret_cast<StemBnLds*>(patch);
+        stem_bn_finalize<256>(L, bn.slot + NMOM, MOM_REPL, blockIdx.x == 0 ? bn.slot : nullptr, w, bias, bn, blockIdx.x == 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { sc[j] = L.sc[32 * j + l31]; sh[j] = L.sh[32 * j + l31]; }
+        __syncthreads();                                          // the patch goes where L was
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = 32 * j + l31;
         wb[j] = stem_weights(w, c, half);
-        b[j] = bias[c]; sc[j] = scale[c]; sh[j] = shift[c];
+        b[j] = bias[c];
+        if (!TRAIN) { sc[j] = scale[c]; sh[j] = shift[c]; }
     }
     const int pp = l31 >> 2, df = (l31 >> 1) & 1, dt = l31 & 1;          // this lane's A row: pooled pixel pp, window (df, dt)
     PatchRegs pre;
@@ -641,12 +749,18 @@ __global__ __launch_bounds__(704) void conv1_bwd_finalize_kernel(const float* __
     (void)dbias;            // d(conv bias) is identically zero under train-mode BN
 }
 
-void launch_moments(const float* img, double* mom, int N, int F, int T, hipStream_t s) {
-    // narrower chunks = more workgroups = more fp64 atomics at the end: 31 / 37 / 55 / 82 us at 128 / 64 / 32 / 16 columns (B = 512)
-    const int tcw = MOM_TC;
-    const int nchunk = ceil_div(T, tcw);
-    const size_t lds = sizeof(float) * (F + 2) * (min(T, tcw) + 2);
-    hipLaunchKernelGGL(conv1_moments_kernel, dim3(N * nchunk), dim3(256), lds, s, img, mom, N, F, T, nchunk, tcw);
+int launch_moments(const float* img_a, const float* img_b, double* rep_a, double* rep_b, int N, int F, int T, hipStream_t s) {
+    const int nband = ceil_div(F, MOM_BAND), nchunk = ceil_div(T, MOM_TC), items = N * nband * nchunk, views = img_b ? 2 : 1;
+    // as many workgroups as the chip holds at four per CU, shared between the views - more only where a lane's fp32 run would
+    // otherwise pass MOM_RUN items
+    static const int resident = getenv("AUDIOSSL_MOM_GRID") ? atoi(getenv("AUDIOSSL_MOM_GRID")) : 1024;
+    const int grid = min(items, max(max(resident / views, 1), ceil_div(items, MOM_RUN)));
+    hipLaunchKernelGGL(conv1_moments_kernel, dim3(grid, views), dim3(256), 0, s, img_a, img_b, rep_a, rep_b, N, F, T, nband, nchunk);
+    return hipGetLastError() == hipSuccess ? ASSL_OK : ASSL_ELAUNCH;
+}
+
+bool moments_shape_ok(int N, int F, int T) {
+    return N > 0 && F >= 2 && F <= 120 && T >= 2 && (long)N * F * T < 0x7FFFFFFFL - 0x1000000L;
 }
 
 }  // namespace
@@ -656,16 +770,25 @@ extern "C" int audiossl_conv1_stats(const float* img, int N, int F, int T, const
                                     float momentum, float eps, double* mom, float* scale, float* shift,
                                     float* save_mean, float* save_rstd, void* stream) {
     ASSL_REQUIRE(img && w && bias && gamma && beta && mom && scale && shift && save_mean && save_rstd);
-    ASSL_REQUIRE(N > 0 && F >= 2 && F <= 120 && T >= 2 && (long)N * F * T < 0x7FFFFFFFL - 0x1000000L);
+    ASSL_REQUIRE(moments_shape_ok(N, F, T));
     hipStream_t s = static_cast<hipStream_t>(stream);
     ASSL_ZERO(mom, sizeof(double) * NMOM * MOM_REPL, s);
-    const long total = (long)N * F * T;
     // every workgroup ends with 54 fp64 atomics; on ONE set of 54 addresses they serialise at the memory side -
     // MOM_REPL replicas of the accumulator, folded by the finalize kernel
-    launch_moments(img, mom, N, F, T, s);
-    hipLaunchKernelGGL(conv1_finalize_kernel, dim3(1), dim3(576), 0, s, mom, w, bias, gamma, beta, running_mean,
-                       running_var, momentum, eps, (double)total, scale, shift, save_mean, save_rstd, MOM_REPL);
+    if (launch_moments(img, nullptr, mom, nullptr, N, F, T, s) != ASSL_OK) return ASSL_ELAUNCH;
+    const StemBn bn = {nullptr, gamma, beta, running_mean, running_var, momentum, eps, (double)((long)N * F * T),
+                       scale, shift, save_mean, save_rstd};
+    hipLaunchKernelGGL(conv1_finalize_kernel, dim3(1), dim3(576), 0, s, mom, w, bias, bn, MOM_REPL);
     ASSL_LAUNCH_CHECK();
+}
+
+// The same for up to two views in one launch, into moment slots the consumer finalizes (conv1_fwd_train): `mom` holds one slot of
+// AUDIOSSL_CONV1_MOM_SLOT doubles per view, img_b == NULL leaves the second slot alone.
+extern "C" int audiossl_conv1_moments_pair(const float* img_a, const float* img_b, int N, int F, int T, double* mom, void* stream) {
+    ASSL_REQUIRE(img_a && mom && moments_shape_ok(N, F, T));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ASSL_ZERO(mom, sizeof(double) * MOM_SLOT * (img_b ? 2 : 1), s);
+    return launch_moments(img_a, img_b, mom + NMOM, mom + MOM_SLOT + NMOM, N, F, T, s);
 }
 
 // ---- the same in two halves, for statistics that are exchanged between ranks in between (SyncBatchNorm of the
@@ -683,10 +806,10 @@ __global__ void conv1_fold_kernel(double* __restrict__ momr) {
     if (c < NMOM) momr[c] = tot[c];
 }
 extern "C" int audiossl_conv1_moments(const float* img, int N, int F, int T, double* mom, void* stream) {
-    ASSL_REQUIRE(img && mom && N > 0 && F >= 2 && F <= 120 && T >= 2 && (long)N * F * T < 0x7FFFFFFFL - 0x1000000L);
+    ASSL_REQUIRE(img && mom && moments_shape_ok(N, F, T));
     hipStream_t s = static_cast<hipStream_t>(stream);
     ASSL_ZERO(mom, sizeof(double) * NMOM * MOM_REPL, s);
-    launch_moments(img, mom, N, F, T, s);
+    if (launch_moments(img, nullptr, mom, nullptr, N, F, T, s) != ASSL_OK) return ASSL_ELAUNCH;
     hipLaunchKernelGGL(conv1_fold_kernel, dim3(1), dim3(64), 0, s, mom);
     ASSL_LAUNCH_CHECK();
 }
@@ -694,8 +817,8 @@ extern "C" int audiossl_conv1_finalize(double* mom_totals, const float* w, const
                                        float* running_mean, float* running_var, float momentum, float eps, double count,
                                        float* scale, float* shift, float* save_mean, float* save_rstd, void* stream) {
     ASSL_REQUIRE(mom_totals && w && bias && gamma && beta && scale && shift && save_mean && save_rstd && count > 1.0);
-    hipLaunchKernelGGL(conv1_finalize_kernel, dim3(1), dim3(576), 0, static_cast<hipStream_t>(stream), mom_totals, w, bias, gamma, beta,
-                       running_mean, running_var, momentum, eps, count, scale, shift, save_mean, save_rstd, 1);
+    const StemBn bn = {nullptr, gamma, beta, running_mean, running_var, momentum, eps, count, scale, shift, save_mean, save_rstd};
+    hipLaunchKernelGGL(conv1_finalize_kernel, dim3(1), dim3(576), 0, static_cast<hipStream_t>(stream), mom_totals, w, bias, bn, 1);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -716,8 +839,26 @@ extern "C" int audiossl_conv1_fwd(int dtype, const float* img, int N, int F, int
         hipLaunchKernelGGL(conv1_fwd_kernel<bf16>, dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift,
                            static_cast<bf16*>(out), N, F, T);
     else
-        hipLaunchKernelGGL(conv1_fwd_mfma_kernel, dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift,
-                           static_cast<bf16*>(out), xl, xs_split, N, F, T);
+        hipLaunchKernelGGL(conv1_fwd_mfma_kernel<false>, dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift,
+                           static_cast<bf16*>(out), xl, xs_split, N, F, T, StemBn{});
+    ASSL_LAUNCH_CHECK();
+}
+
+// conv1_finalize + conv1_fwd(dtype 1) in one launch: `mom` is the view's moment slot as conv1_moments_pair left it; the totals end
+// up in mom[0..53], scale / shift / mean / rstd and the running buffers are written as conv1_finalize writes them (same bits).
+extern "C" int audiossl_conv1_fwd_train(const float* img, int N, int F, int T, double* mom, double count, const float* w,
+                                        const float* bias, const float* gamma, const float* beta, float* running_mean,
+                                        float* running_var, float momentum, float eps, float* scale, float* shift,
+                                        float* save_mean, float* save_rstd, void* out, float* xl, void* stream) {
+    ASSL_REQUIRE(img && mom && w && bias && gamma && beta && scale && shift && save_mean && save_rstd && out && count > 1.0);
+    ASSL_REQUIRE(N > 0 && F >= 2 && F <= 126 && T >= 2 && (F % 2) == 0 && (!running_mean == !running_var));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int xs_split = 4;                                       // AUDIOSSL_CONV1_XL_PARTS in include/audiossl_hip.h
+    const int grid = xl ? N * xs_split : min(N * (T / 2), 2048);
+    const size_t lds = max(sizeof(float) * (((F + 2) * 4 + 3) & ~3) + sizeof(bf16) * (F / 2) * 64, sizeof(StemBnLds));
+    const StemBn bn = {mom, gamma, beta, running_mean, running_var, momentum, eps, count, scale, shift, save_mean, save_rstd};
+    hipLaunchKernelGGL(conv1_fwd_mfma_kernel<true>, dim3(grid), dim3(256), lds, s, img, w, bias, (const float*)nullptr,
+                       (const float*)nullptr, static_cast<bf16*>(out), xl, xs_split, N, F, T, bn);
     ASSL_LAUNCH_CHECK();
 }
 

@@ -397,12 +397,34 @@ def _col_buffer(dtype, Nimg, T1, F1, like):
     return _empty((Nimg * T1 * F1, 576), N.torch_dtype(dtype), like=like)
 
 
+MOM_SLOT = 17 * 54             # AUDIOSSL_CONV1_MOM_SLOT: doubles per view's stem moment slot (54 totals, then 16 replica sets)
+
+
+def stem_fused(dtype, train=True):
+    """True when the stem runs as moments + ONE forward launch that finalizes its own batch statistics (bf16 MFMA stem, training,
+    no SyncBatchNorm); every other flavour keeps conv1_stats / conv1_moments + conv1_finalize + conv1_fwd."""
+    return bool(train) and dtype == N.BF16 and not HP and not _STEM_VALU and SYNC_BN is None
+
+
+def stem_moments_pair(xa, xb=None):
+    """Tap moments of one or two view batches [N,1,F,T] fp32 (same shape) in one launch -> [views, MOM_SLOT] float64; row v is the
+    `stem_moments` argument of the encoder_forward call on that view."""
+    Nimg, _, F, T = xa.shape
+    assert xb is None or xb.shape == xa.shape
+    mom = ARENA.scratch((1 if xb is None else 2, MOM_SLOT), torch.float64, xa)
+    N.call("conv1_moments_pair", xa.reshape(Nimg, F, T).contiguous(), None if xb is None else xb.reshape(Nimg, F, T).contiguous(),
+           Nimg, F, T, mom)
+    return mom
+
+
 def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_running=True, want_layers=True, Wc=None,
-                    layer_out=None, before_fc=None):
+                    layer_out=None, before_fc=None, stem_moments=None):
     """P: dict of fp32 device tensors with the reference's state_dict keys (features_1.0.weight, ...).
     x [N,1,F,T] fp32.  keep: uint8 [N*T3, d] dropout keep-mask or None (no dropout).
     Wc: optional {"fc.0.weight", "fc.3.weight"} already in the activation dtype (flat shadow); layer_out: optional
     (x1, x2, x3) output buffers [N, F*64] (e.g. halves of the stacked projector inputs).
+    stem_moments: this view's row of `stem_moments_pair` when the caller has already taken the stem's tap moments (both views of a
+    step in one launch); only where `stem_fused(dtype, train)` holds.
     Returns (x1, x2, x3, H2 [N,T3,d]) in the activation dtype and the ctx for the backward."""
     Nimg, _, F, T = x.shape
     assert F == 64, "the HIP encoder is built for n_mels = 64 (the reference's only setting)"
@@ -415,11 +437,20 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     w1 = P["features_1.0.weight"].reshape(64, 9)
     b1 = P["features_1.0.bias"]
     g1, be1 = P["features_1.1.weight"], P["features_1.1.bias"]
+    # bf16: the stem conv is a bf16 MFMA; bf16_hp keeps the fp32 VALU convolution (exact pooling arg-max) with bf16 output
+    c.stem_mfma = dtype == N.BF16 and not HP and not _STEM_VALU
+    fused = stem_fused(dtype, train)
+    assert stem_moments is None or fused, "precomputed stem moments are for the fused bf16 training stem only"
+    rm1 = rv1 = None
     if train:
-        c.mom1 = ARENA.scratch((16 * 54,), torch.float64, x)         # 16 replicas of the 54 tap moments; totals end up in [0:54]
         c.sc1, c.sh1, c.mean1, c.rstd1 = (_empty((64,), torch.float32, like=x) for _ in range(4))
         rm1 = P["features_1.1.running_mean"] if update_running else None
         rv1 = P["features_1.1.running_var"] if update_running else None
+    if fused:
+        # moment slot of this view: the forward launch below folds its replicas; the totals end up in [0:54] for the backward
+        c.mom1 = stem_moments if stem_moments is not None else stem_moments_pair(x)[0]
+    elif train:
+        c.mom1 = ARENA.scratch((16 * 54,), torch.float64, x)         # 16 replicas of the 54 tap moments; totals end up in [0:54]
         if SYNC_BN is None:
             N.call("conv1_stats", img, Nimg, F, T, w1, b1, g1, be1, rm1, rv1, BN_MOMENTUM, BN_EPS, c.mom1, c.sc1, c.sh1, c.mean1, c.rstd1)
         else:                                     # this rank's tap moments stay in c.mom1 (the backward needs the local sums)
@@ -431,15 +462,17 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
         c.sc1, c.sh1 = _bn_eval(x, 64, g1, be1, P["features_1.1.running_mean"], P["features_1.1.running_var"])
     T1, F1 = T // 2, F // 2
     c.P1 = _empty((Nimg, T1, F1, 64), td, like=x)
-    # bf16: the stem conv is a bf16 MFMA; bf16_hp keeps the fp32 VALU convolution (exact pooling arg-max) with bf16 output
-    c.stem_mfma = dtype == N.BF16 and not HP and not _STEM_VALU
     x1 = x2 = x3 = None
     if want_layers:
         x1, x2, x3 = layer_out if layer_out is not None else (_empty((Nimg, f * 64), td, like=x) for f in (F // 2, F // 4, F // 8))
     # the MFMA stem also leaves x_1 (mean over time of its pooled output) when an fp32 buffer is wanted for it
     x1_fused = c.stem_mfma and x1 is not None and x1.dtype == torch.float32 and x1.is_contiguous()
     x1_parts = _empty((4, Nimg, (F // 2) * 64), torch.float32, like=x) if x1_fused else None        # AUDIOSSL_CONV1_XL_PARTS
-    N.call("conv1_fwd", dtype if (dtype == N.F32 or c.stem_mfma) else 2, img, Nimg, F, T, w1, b1, c.sc1, c.sh1, c.P1, x1_parts)
+    if fused:
+        N.call("conv1_fwd_train", img, Nimg, F, T, c.mom1, float(Nimg * F * T), w1, b1, g1, be1, rm1, rv1, BN_MOMENTUM, BN_EPS,
+               c.sc1, c.sh1, c.mean1, c.rstd1, c.P1, x1_parts)
+    else:
+        N.call("conv1_fwd", dtype if (dtype == N.F32 or c.stem_mfma) else 2, img, Nimg, F, T, w1, b1, c.sc1, c.sh1, c.P1, x1_parts)
     col = _col_buffer(dtype, Nimg, T1, F1, x)
     bn2 = (P["features_2.1.weight"], P["features_2.1.bias"], P["features_2.1.running_mean"], P["features_2.1.running_var"])
     packs = [_empty((64, 576), td, like=x) for _ in range(4)]         # both layers' (forward, data-gradient) layouts: one launch

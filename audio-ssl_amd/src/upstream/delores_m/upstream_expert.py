@@ -31,6 +31,7 @@ _GRADS_ZERO = os.environ.get("AUDIOSSL_GRADS_ZERO", "1") != "0"          # 0: we
 _DY_EVENT = os.environ.get("AUDIOSSL_DY_EVENT", "1") != "0"              # 0: the main stream waits for the whole heads stream
 _LATE_JOIN = os.environ.get("AUDIOSSL_LATE_JOIN", "1") != "0"            # 0: join the heads before the whole encoder backward
 _SGD_ASIDE = os.environ.get("AUDIOSSL_SGD_ASIDE", "1") != "0"            # 0: the early head-segment SGD is issued on the main stream
+_STEM_PAIR = os.environ.get("AUDIOSSL_STEM_PAIR", "0") == "1"            # 1: both views' stem moments in one launch before the key stream forks
 
 
 def _world():
@@ -106,6 +107,17 @@ class Upstream_Expert(MocoQueueMixin, FusedExpertMixin, UpstreamModule):
         # stacked projector inputs: rows [0,B) from the query encoder, [B,2B) from the key encoder
         Ys = R.alloc("Ys", lambda: [torch.empty(2 * B, f, dtype=E.pooled_dtype(dt), device=dev) for f in (2048, 1024, 512)])
 
+        # ---- stem statistics of BOTH views in one launch at the head of the main stream, before the key stream forks: off by default.
+        #      Measured at B = 512 it gains nothing over each encoder taking its own moments - the pair
+        #      launch shares the CUs with the next batch's log-mel (both bound by VALU issue: 22 us alone, 82 us there) and the key
+        #      stream's EMA now waits for it: 1.894-1.922 ms against 1.869-1.884 ms.  Data-parallel ranks shuffle the key batch between
+        #      ranks first and could not use it anyway.
+        moms = None
+        if _STEM_PAIR and not ddp and E.stem_fused(dt, self.training):
+            moms = R.phase("stem_moments", lambda: E.stem_moments_pair(img_q, img_k))
+            if not E.ONE_STREAM:
+                moms.record_stream(self._key_stream.stream(dev))
+
         # ---- key encoder (no gradient) on its own stream, concurrent with the query encoder: EMA first, then forward
         def key_phase(x):
             self._momentum_update_key_encoder(shadow_dtype=dt)
@@ -113,7 +125,8 @@ class Upstream_Expert(MocoQueueMixin, FusedExpertMixin, UpstreamModule):
             Wk = self.flat_k.shadow_dict()
             keepk = ek.encoder.next_keep_mask(B, x.shape[-1])
             _, _, _, Hk, _ = E.encoder_forward(ek.encoder.param_dict(), x, dt, keep=keepk, p_drop=0.3, train=self.training,
-                                               Wc=strip(Wk, "encoder."), layer_out=tuple(y[B:] for y in Ys))
+                                               Wc=strip(Wk, "encoder."), layer_out=tuple(y[B:] for y in Ys),
+                                               stem_moments=None if moms is None else moms[1])
             yk, _ = E.maxmean_forward(dt, Hk)
             wk = Wk["fc.weight"]
             return E.linear_fwd(dt, yk, wk, B, wk.shape[0], wk.shape[1], bias=ek.fc.bias.data, out_f32=1)
@@ -169,7 +182,8 @@ class Upstream_Expert(MocoQueueMixin, FusedExpertMixin, UpstreamModule):
             keep = eq.encoder.next_keep_mask(B, img_q.shape[-1])
             _, _, _, Hq, cq = E.encoder_forward(eq.encoder.param_dict(), img_q, dt, keep=keep, p_drop=0.3, train=self.training,
                                                 Wc=strip(Wq, "encoder."), layer_out=tuple(y[:B] for y in Ys),
-                                                before_fc=(lambda: self._prep_stream.join(dev)) if (_PREP_ASIDE and busy) else None)
+                                                before_fc=(lambda: self._prep_stream.join(dev)) if (_PREP_ASIDE and busy) else None,
+                                                stem_moments=None if moms is None else moms[0])
             yq, argq = E.maxmean_forward(dt, Hq)
             q = E.linear_fwd(dt, yq, wq, B, wq.shape[0], wq.shape[1], bias=eq.fc.bias.data, out_f32=1)
             return loss, wq, Hq, cq, yq, argq, q

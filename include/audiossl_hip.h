@@ -146,6 +146,22 @@ int audiossl_conv1_stats(const float* img, int N, int F, int T, const float* w, 
 #define AUDIOSSL_CONV1_XL_PARTS 4
 int audiossl_conv1_fwd(int dtype, const float* img, int N, int F, int T, const float* w, const float* bias,
                        const float* scale, const float* shift, void* out, float* xl, void* stream);
+/* Training forward of the bf16 stem in two launches.  A view's MOMENT SLOT is AUDIOSSL_CONV1_MOM_SLOT doubles: [0..53] the 54 tap-moment
+ * totals (9 first moments in tap order kh*3+kw, then the 45 second moments of pairs a <= b, row-major upper triangle), followed by 16
+ * replica sets of 54 that the moments kernel adds into.
+ * conv1_moments_pair: tap moments of img_a and (unless NULL) img_b, both [N][F][T], in ONE launch; `mom` = one slot per view, slot 1
+ *   is left alone when img_b is NULL.  Clears the slots it fills unless the caller declared them pre-zeroed; afterwards the replica
+ *   sets are filled and [0..53] is still zero.
+ * conv1_fwd_train: conv1_finalize + conv1_fwd(dtype 1) in one launch: every workgroup folds the slot's replicas in replica order and
+ *   derives scale / shift itself; the first also writes scale, shift, save_mean, save_rstd, the running buffers (may both be NULL)
+ *   and the totals to mom[0..53] (conv1_bwd reads them there).  count = N*F*T.  Same bits as the two-launch path given the same
+ *   totals. */
+#define AUDIOSSL_CONV1_MOM_SLOT (17 * 54)
+int audiossl_conv1_moments_pair(const float* img_a, const float* img_b, int N, int F, int T, double* mom, void* stream);
+int audiossl_conv1_fwd_train(const float* img, int N, int F, int T, double* mom, double count, const float* w, const float* bias,
+                             const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
+                             float eps, float* scale, float* shift, float* save_mean, float* save_rstd, void* out, float* xl,
+                             void* stream);
 /* conv1_bwd: dtype = type of the pooled gradient dP (0 fp32, 1 bf16); with conv_dtype 1 (MFMA recompute) dxl stays fp32 whatever
  * dtype says, with conv_dtype 0 dP and dxl share it */
 int audiossl_conv1_bwd(int dtype, int conv_dtype, const float* img, int N, int F, int T, const float* w, const float* bias,

@@ -24,7 +24,13 @@ img = torch.randn(Nimg, F, T, device="cuda"); w = torch.randn(64, 1, 3, 3, devic
 gm = torch.rand(64, device="cuda") + 0.5; bt = torch.randn(64, device="cuda"); rm = torch.zeros(64, device="cuda"); rv = torch.ones(64, device="cuda")
 mom = torch.zeros(16 * 54, dtype=torch.float64, device="cuda"); st = torch.empty(4, 64, device="cuda")
 t = timeit(lambda: N.call("conv1_stats", img, Nimg, F, T, w, b, gm, bt, rm, rv, 0.1, 1e-5, mom, st[0], st[1], st[2], st[3])); print(f"conv1_stats {t:7.1f} us")
+img2 = torch.randn(Nimg, F, T, device="cuda"); slots = torch.zeros(2, 17 * 54, dtype=torch.float64, device="cuda")   # one moment slot per view
+t = timeit(lambda: N.call("conv1_moments_pair", img, None, Nimg, F, T, slots)); print(f"conv1_moments_pair (one view) {t:7.1f} us")
+t = timeit(lambda: N.call("conv1_moments_pair", img, img2, Nimg, F, T, slots)); print(f"conv1_moments_pair (two views) {t:7.1f} us")
 P = torch.empty(Nimg, T // 2, F // 2, 64, device="cuda", dtype=torch.bfloat16)
 t = timeit(lambda: N.call("conv1_fwd", 1, img, Nimg, F, T, w, b, st[0], st[1], P, None)); print(f"conv1_fwd (MFMA) {t:7.1f} us")
 xl = torch.empty(4, Nimg, (F // 2) * 64, device="cuda")
+for name, x in (("", None), (" + layer mean", xl)):
+    t = timeit(lambda: N.call("conv1_fwd_train", img, Nimg, F, T, slots[0], float(Nimg * F * T), w, b, gm, bt, rm, rv, 0.1, 1e-5,
+                              st[0], st[1], st[2], st[3], P, x)); print(f"conv1_fwd_train (finalize + MFMA){name} {t:7.1f} us")
 t = timeit(lambda: N.call("conv1_fwd", 1, img, Nimg, F, T, w, b, st[0], st[1], P, xl)); print(f"conv1_fwd (MFMA) + layer mean {t:7.1f} us")
