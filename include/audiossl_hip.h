@@ -210,7 +210,9 @@ int audiossl_bn_relu_pool_bwd_p(int dtype, int ydtype, int gdtype, const void* Y
  *             -> bn_finalize(count = global)
  *   backward: bn_relu_pool_bwd_stats -> [all-reduce stat[0..127]] -> bn_relu_pool_bwd_apply;  conv1_bwd_sums -> [all-reduce lstat]
  *             -> conv1_bwd_finalize;  colbn_bwd_stats -> [all-reduce tmp] -> colbn_bwd_apply (+ add_d2f of the rank's own sums).
- * Parameter gradients always come from the rank's own sums (the data-parallel gradient all-reduce sums them afterwards). */
+ * Parameter gradients always come from the rank's own sums (the data-parallel gradient all-reduce sums them afterwards).
+ * conv1_bwd_finalize's `mom` is the rank's OWN tap-moment totals (what conv1_moments left in mom[0..53] for this rank's images), not
+ * the all-reduced ones: they weight the two global means in this rank's share of dW; only `gstat` and `count_global` are global. */
 int audiossl_conv1_moments(const float* img, int N, int F, int T, double* mom, void* stream);
 int audiossl_conv1_finalize(double* mom_totals, const float* w, const float* bias, const float* gamma, const float* beta,
                             float* running_mean, float* running_var, float momentum, float eps, double count, float* scale,
