@@ -477,8 +477,6 @@ __global__ void unpack_conv_dw_kernel(const float* __restrict__ dWp, float* __re
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16) do { if ((dtype) == 0) { CALL_F32; } else { CALL_BF16; } } while (0)
-
 extern "C" int audiossl_colstats(int dtype, const void* x, int groups, long M, int C, long ld, int want_sq, double* sum,
                                  double* sumsq, void* stream) {
     ASSL_REQUIRE(x && sum && groups > 0 && M > 0 && C > 0 && (C % 8) == 0 && (ld % 8) == 0);
@@ -496,10 +494,10 @@ extern "C" int audiossl_colstats(int dtype, const void* x, int groups, long M, i
     it = it < 1 ? 1 : (it > 128 ? 128 : it);
     const int rpb = 32 * (int)it;
     const dim3 grid(ceil_div(M, rpb), slabs, groups);
-#define CS(TT, SQ) hipLaunchKernelGGL((colstats_kernel<TT, SQ>), grid, dim3(256), 0, s, static_cast<const TT*>(x), M, C, ld, rpb, sum, sumsq)
-    if (dtype == 0) { if (want_sq) CS(float, true); else CS(float, false); }
-    else            { if (want_sq) CS(bf16, true);  else CS(bf16, false); }
-#undef CS
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (want_sq) hipLaunchKernelGGL((colstats_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T*>(x), M, C, ld, rpb, sum, sumsq);
+        else         hipLaunchKernelGGL((colstats_kernel<T, false>), grid, dim3(256), 0, s, static_cast<const T*>(x), M, C, ld, rpb, sum, sumsq);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -519,11 +517,10 @@ extern "C" int audiossl_bn_relu_pool_fwd(int dtype, int ydtype, const void* Y, c
     ASSL_REQUIRE(Y && scale && shift && P && N > 0 && Ti >= 2 && Fi >= 2 && (Fi % 2) == 0 && (dtype == 0 || dtype == 1));
     ASSL_REQUIRE(ydtype == 0 || ydtype == dtype);
     const long total = (long)N * (Ti / 2) * (Fi / 2) * 8;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define PF(TY, TO) hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<TY, TO>), dim3(ceil_div(total, 256)), dim3(256), 0, s, \
-        static_cast<const TY*>(Y), scale, shift, static_cast<TO*>(P), N, Ti, Fi)
-    if (dtype == 0) PF(float, float); else if (ydtype == 0) PF(float, bf16); else PF(bf16, bf16);
-#undef PF
+    assl_dispatch(dtype, [&](auto to, auto ty) { using TO = typename decltype(to)::type; using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<TY, TO>), dim3(ceil_div(total, 256)), dim3(256), 0, S_(stream),
+                           static_cast<const TY*>(Y), scale, shift, static_cast<TO*>(P), N, Ti, Fi);
+    }, ydtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -536,23 +533,20 @@ extern "C" int audiossl_bn_relu_pool_train_fwd(int dtype, int ydtype, const void
     ASSL_REQUIRE(stat_replicas >= 1 && (stat_replicas == 1 || sumsq == sum + 64));
     ASSL_REQUIRE(N > 0 && Ti >= 2 && Fi >= 2 && (Fi % 2) == 0 && (dtype == 0 || dtype == 1) && (ydtype == 0 || ydtype == dtype));
     const long total = (long)N * (Ti / 2) * (Fi / 2) * 8;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define PF(TY, TO) hipLaunchKernelGGL((bn_relu_pool_train_fwd_kernel<TY, TO>), dim3(ceil_div(total, 256)), dim3(256), 0, s,          \
-        static_cast<const TY*>(Y), sum, sumsq, stat_replicas, count, gamma, beta, running_mean, running_var, momentum, eps,      \
-        static_cast<TO*>(P),                                                                                                      \
-        scale, shift, save_mean, save_rstd, N, Ti, Fi)
-    if (dtype == 0) PF(float, float); else if (ydtype == 0) PF(float, bf16); else PF(bf16, bf16);
-#undef PF
+    assl_dispatch(dtype, [&](auto to, auto ty) { using TO = typename decltype(to)::type; using TY = typename decltype(ty)::type;
+        hipLaunchKernelGGL((bn_relu_pool_train_fwd_kernel<TY, TO>), dim3(ceil_div(total, 256)), dim3(256), 0, S_(stream),
+                           static_cast<const TY*>(Y), sum, sumsq, stat_replicas, count, gamma, beta, running_mean, running_var,
+                           momentum, eps, static_cast<TO*>(P), scale, shift, save_mean, save_rstd, N, Ti, Fi);
+    }, ydtype);
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_tmean_fwd(int dtype, int out_f32, const void* P, void* xl, int N, int To, int Fo, void* stream) {
     ASSL_REQUIRE(P && xl && N > 0 && To > 0 && Fo > 0 && (dtype == 0 || dtype == 1));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define TM(TI, TO_) hipLaunchKernelGGL((tmean_fwd_kernel<TI, TO_>), dim3(ceil_div(Fo * 8, 64), N), dim3(256), 0, s, \
-        static_cast<const TI*>(P), static_cast<TO_*>(xl), N, To, Fo)
-    if (dtype == 0) TM(float, float); else if (out_f32) TM(bf16, float); else TM(bf16, bf16);
-#undef TM
+    assl_dispatch(dtype, [&](auto ti, auto to) { using TI = typename decltype(ti)::type; using TO = typename decltype(to)::type;
+        hipLaunchKernelGGL((tmean_fwd_kernel<TI, TO>), dim3(ceil_div(Fo * 8, 64), N), dim3(256), 0, S_(stream), static_cast<const TI*>(P),
+                           static_cast<TO*>(xl), N, To, Fo);
+    }, out_f32 ? 0 : dtype);      // the output is the wide tensor here
     ASSL_LAUNCH_CHECK();
 }
 
@@ -562,12 +556,11 @@ extern "C" int audiossl_tmean3_fwd(int dtype, int out_f32, const void* P1, void*
     ASSL_REQUIRE(x1 && P2 && x2 && P3 && x3 && N > 0 && To1 > 0 && To2 > 0 && To3 > 0 && Fo1 > 0 && Fo2 > 0 && Fo3 > 0);
     ASSL_REQUIRE((P1 != nullptr) != (x1_parts != nullptr) && (!x1_parts || (out_f32 && dtype == 1)));
     ASSL_REQUIRE(dtype == 0 || dtype == 1);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     Tmean3 a{{P1, P2, P3}, {x1, x2, x3}, {To1, To2, To3}, {Fo1, Fo2, Fo3}, x1_parts};
     const int gx = ceil_div(max(Fo1, max(Fo2, Fo3)) * 8, 64);
-#define TM3(TI, TO_) hipLaunchKernelGGL((tmean3_fwd_kernel<TI, TO_>), dim3(gx, N, 3), dim3(256), 0, s, a, N)
-    if (dtype == 0) TM3(float, float); else if (out_f32) TM3(bf16, float); else TM3(bf16, bf16);
-#undef TM3
+    assl_dispatch(dtype, [&](auto ti, auto to) { using TI = typename decltype(ti)::type; using TO = typename decltype(to)::type;
+        hipLaunchKernelGGL((tmean3_fwd_kernel<TI, TO>), dim3(gx, N, 3), dim3(256), 0, S_(stream), a, N);
+    }, out_f32 ? 0 : dtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -598,24 +591,23 @@ static int bn_relu_pool_bwd_run(int phase, int dtype, int ydtype, int gdtype, co
     const float inv_count = (float)(1.0 / (phase == 2 ? count : (double)N * Ti * Fi));
     float* apply_stat = phase == 2 ? const_cast<float*>(gstat) : stat;
     const int fold = phase == 0;               // one rank: fold + parameter gradients inside the apply pass (no stat_reduce / add_stat launch)
-#define BW(TY, AP, TG, TO, ST) hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<TY, AP, TG, TO>), dim3(grid), dim3(256), 0, s,              \
-        static_cast<const TY*>(Y), static_cast<const TG*>(dP), static_cast<const TG*>(dxl), inv_To, scale, shift, mean, rstd, ST, \
-        inv_count, static_cast<TO*>(dY), N, Ti, Fi, (AP) ? fold : 0, dgamma, dbeta)
-#define BWP(TG, TO) hipLaunchKernelGGL((bn_pool_bwd_stats_p_kernel<TO, TG>), dim3(pgrid), dim3(256), 0, s, static_cast<const TO*>(P),          \
-        static_cast<const TG*>(dP), static_cast<const TG*>(dxl), inv_To, scale, shift, mean, rstd, stat, N, Ti / 2, Fi / 2)
-#define BW2(TY, TG, TO) do { if (phase != 2) { if (P) BWP(TG, TO); else BW(TY, false, TG, TO, stat);                                       \
-                                               if (!fold) hipLaunchKernelGGL(stat_reduce_kernel, dim3(1), dim3(128), 0, s, stat); }          \
-                             if (phase != 1) BW(TY, true, TG, TO, apply_stat); } while (0)
     const long ptotal = (long)N * (Ti / 2) * (Fi / 2) * 8;
     const int pgrid = (int)min((long)2048, (ptotal + 255) / 256);         // 2,048 x 256 threads: a multiple of 8, see the kernel
-    if (dtype == 0) BW2(float, float, float);
-    else if (ydtype == 0 && gdtype == 0) BW2(float, float, bf16);
-    else if (ydtype == 0) BW2(float, bf16, bf16);
-    else if (gdtype == 0) BW2(bf16, float, bf16);
-    else BW2(bf16, bf16, bf16);
-#undef BW2
-#undef BWP
-#undef BW
+    assl_dispatch(dtype, [&](auto to, auto ty, auto tg) {
+        using TO = typename decltype(to)::type; using TY = typename decltype(ty)::type; using TG = typename decltype(tg)::type;
+        const TY* y = static_cast<const TY*>(Y);
+        const TG *g = static_cast<const TG*>(dP), *gx = static_cast<const TG*>(dxl);
+        TO* dy = static_cast<TO*>(dY);
+        if (phase != 2) {
+            if (P) hipLaunchKernelGGL((bn_pool_bwd_stats_p_kernel<TO, TG>), dim3(pgrid), dim3(256), 0, s, static_cast<const TO*>(P), g, gx,
+                                      inv_To, scale, shift, mean, rstd, stat, N, Ti / 2, Fi / 2);
+            else hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<TY, false, TG, TO>), dim3(grid), dim3(256), 0, s, y, g, gx, inv_To, scale,
+                                    shift, mean, rstd, stat, inv_count, dy, N, Ti, Fi, 0, dgamma, dbeta);
+            if (!fold) hipLaunchKernelGGL(stat_reduce_kernel, dim3(1), dim3(128), 0, s, stat);
+        }
+        if (phase != 1) hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<TY, true, TG, TO>), dim3(grid), dim3(256), 0, s, y, g, gx, inv_To,
+                                           scale, shift, mean, rstd, apply_stat, inv_count, dy, N, Ti, Fi, fold, dgamma, dbeta);
+    }, ydtype, gdtype);
     if (phase == 2) hipLaunchKernelGGL(add_stat_kernel, dim3(1), dim3(64), 0, s, stat, dgamma, dbeta);
     ASSL_LAUNCH_CHECK();
 }
@@ -652,32 +644,27 @@ extern "C" int audiossl_im2col3x3(int dtype, const void* X, void* col, int N, in
     ASSL_REQUIRE(X && col && N > 0 && Ti > 0 && Fi > 0 && (dtype == 0 || dtype == 1));
     const long total = (long)N * Ti * Fi * 72;
     ASSL_REQUIRE((total + 255) / 256 < 2147483647L);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DISPATCH_T(dtype,
-        hipLaunchKernelGGL(im2col_kernel<float>, dim3(ceil_div(total, 256)), dim3(256), 0, s, static_cast<const float*>(X),
-                           static_cast<float*>(col), N, Ti, Fi),
-        hipLaunchKernelGGL(im2col_kernel<bf16>, dim3(ceil_div(total, 256)), dim3(256), 0, s, static_cast<const bf16*>(X),
-                           static_cast<bf16*>(col), N, Ti, Fi));
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(im2col_kernel<T>, dim3(ceil_div(total, 256)), dim3(256), 0, S_(stream), static_cast<const T*>(X),
+                           static_cast<T*>(col), N, Ti, Fi);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_pack_conv_w(int dtype, const float* W, void* Wf, void* Wd, void* stream) {
     ASSL_REQUIRE(W && Wf && Wd && (dtype == 0 || dtype == 1));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DISPATCH_T(dtype,
-        hipLaunchKernelGGL(pack_conv_w_kernel<float>, dim3(144), dim3(256), 0, s, W, static_cast<float*>(Wf), static_cast<float*>(Wd)),
-        hipLaunchKernelGGL(pack_conv_w_kernel<bf16>, dim3(144), dim3(256), 0, s, W, static_cast<bf16*>(Wf), static_cast<bf16*>(Wd)));
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_conv_w_kernel<T>, dim3(144), dim3(256), 0, S_(stream), W, static_cast<T*>(Wf), static_cast<T*>(Wd));
+    });
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_pack_conv_w2(int dtype, const float* Wa, void* Wfa, void* Wda, const float* Wb, void* Wfb, void* Wdb, void* stream) {
     ASSL_REQUIRE(Wa && Wfa && Wda && Wb && Wfb && Wdb && (dtype == 0 || dtype == 1));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DISPATCH_T(dtype,
-        hipLaunchKernelGGL(pack_conv_w2_kernel<float>, dim3(144, 2), dim3(256), 0, s, Wa, static_cast<float*>(Wfa), static_cast<float*>(Wda),
-                           Wb, static_cast<float*>(Wfb), static_cast<float*>(Wdb)),
-        hipLaunchKernelGGL(pack_conv_w2_kernel<bf16>, dim3(144, 2), dim3(256), 0, s, Wa, static_cast<bf16*>(Wfa), static_cast<bf16*>(Wda),
-                           Wb, static_cast<bf16*>(Wfb), static_cast<bf16*>(Wdb)));
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_conv_w2_kernel<T>, dim3(144, 2), dim3(256), 0, S_(stream), Wa, static_cast<T*>(Wfa), static_cast<T*>(Wda), Wb,
+                           static_cast<T*>(Wfb), static_cast<T*>(Wdb));
+    });
     ASSL_LAUNCH_CHECK();
 }
 

@@ -41,7 +41,7 @@ static inline hipError_t assl_zero_async(void* p, size_t bytes, hipStream_t s) {
 extern const char* g_assl_last_kernel;
 #define ASSL_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return ASSL_ELAUNCH; return ASSL_OK; } while (0)
 
-typedef __bf16 bf16;
+#include "dispatch.h"      // bf16, TypeTag / assl_dispatch / assl_rows, S_ / GRID1
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;

@@ -876,24 +876,18 @@ static int conv1_bwd_main(int dtype, int conv_dtype, const float* img, int N, in
     const int grid = min(N * (T / 2), bwd_grid);
     const size_t lds = sizeof(float) * (F + 2) * 4;
     const float inv_To = 1.f / (float)(T / 2);
-    if (conv_dtype == 1 && F == 64 && dtype == 0)
-        hipLaunchKernelGGL((conv1_bwd_mfma_kernel<true, float>), dim3(grid), dim3(256), lds + 2 * 2048 * sizeof(float), s, img, w, bias, scale,
-                           shift, mean, rstd, static_cast<const float*>(dP), static_cast<const float*>(dxl), inv_To, acc, N, F, T);
-    else if (conv_dtype == 1 && F == 64)
-        hipLaunchKernelGGL((conv1_bwd_mfma_kernel<true, bf16>), dim3(grid), dim3(256), lds + 2 * 2048 * sizeof(float), s, img, w, bias, scale,
-                           shift, mean, rstd, static_cast<const bf16*>(dP), static_cast<const float*>(dxl), inv_To, acc, N, F, T);
-    else if (conv_dtype == 1 && dtype == 0)
-        hipLaunchKernelGGL((conv1_bwd_mfma_kernel<false, float>), dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift, mean, rstd,
-                           static_cast<const float*>(dP), static_cast<const float*>(dxl), inv_To, acc, N, F, T);
-    else if (conv_dtype == 1)
-        hipLaunchKernelGGL((conv1_bwd_mfma_kernel<false, bf16>), dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift, mean, rstd,
-                           static_cast<const bf16*>(dP), static_cast<const float*>(dxl), inv_To, acc, N, F, T);
-    else if (dtype == 0)
-        hipLaunchKernelGGL(conv1_bwd_kernel<float>, dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift, mean, rstd,
-                           static_cast<const float*>(dP), static_cast<const float*>(dxl), inv_To, acc, N, F, T);
-    else
-        hipLaunchKernelGGL(conv1_bwd_kernel<bf16>, dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift, mean, rstd,
-                           static_cast<const bf16*>(dP), static_cast<const bf16*>(dxl), inv_To, acc, N, F, T);
+    auto mfma = [&](auto slab, size_t shmem) {                    // the slab kernel (F == 64) takes 16 KB more LDS
+        assl_dispatch(dtype, [&](auto tg) { using TG = typename decltype(tg)::type;
+            hipLaunchKernelGGL((conv1_bwd_mfma_kernel<slab(), TG>), dim3(grid), dim3(256), shmem, s, img, w, bias, scale, shift, mean, rstd,
+                               static_cast<const TG*>(dP), static_cast<const float*>(dxl), inv_To, acc, N, F, T);
+        });
+    };
+    if (conv_dtype == 1 && F == 64) mfma(std::true_type{}, lds + 2 * 2048 * sizeof(float));
+    else if (conv_dtype == 1) mfma(std::false_type{}, lds);
+    else assl_dispatch(dtype, [&](auto tg) { using TG = typename decltype(tg)::type;
+        hipLaunchKernelGGL(conv1_bwd_kernel<TG>, dim3(grid), dim3(256), lds, s, img, w, bias, scale, shift, mean, rstd,
+                           static_cast<const TG*>(dP), static_cast<const TG*>(dxl), inv_To, acc, N, F, T);
+    });
     return ASSL_OK;
 }
 

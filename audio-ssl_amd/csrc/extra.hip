@@ -269,8 +269,6 @@ __global__ __launch_bounds__(256) void larc_update_kernel(float* __restrict__ p,
 
 }  // namespace
 
-#define S_(stream) static_cast<hipStream_t>(stream)
-
 extern "C" int audiossl_ntxent_fwd(const float* sim, int N, int B, float* lse, float* loss_out, void* stream) {
     ASSL_REQUIRE(sim && lse && loss_out && N > 1 && B > 0 && B < N);
     hipLaunchKernelGGL(ntxent_fwd_kernel, dim3(N), dim3(256), 0, S_(stream), sim, N, B, lse, loss_out);
@@ -281,8 +279,9 @@ extern "C" int audiossl_ntxent_bwd(int dtype, const float* sim, const float* lse
                                    void* stream) {
     ASSL_REQUIRE(sim && lse && dsim && N > 1 && B > 0 && (dtype == 0 || dtype == 1));
     dim3 grid(ceil_div(N, 256), N);
-    if (dtype == 0) hipLaunchKernelGGL(ntxent_bwd_kernel<float>, grid, dim3(256), 0, S_(stream), sim, lse, N, B, gscale, (float*)dsim);
-    else            hipLaunchKernelGGL(ntxent_bwd_kernel<bf16>, grid, dim3(256), 0, S_(stream), sim, lse, N, B, gscale, (bf16*)dsim);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(ntxent_bwd_kernel<T>, grid, dim3(256), 0, S_(stream), sim, lse, N, B, gscale, static_cast<T*>(dsim));
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -328,8 +327,10 @@ extern "C" int audiossl_ce_rows(int dtype, const float* logits, const long long*
     hipStream_t s = S_(stream);
     ASSL_ZERO_ALWAYS(cnt, sizeof(int), s);
     hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(256), 0, s, target, B, ignore_index, cnt);
-    if (dtype == 0) hipLaunchKernelGGL(ce_rows_kernel<float>, dim3(B), dim3(256), 0, s, logits, target, K, ignore_index, cnt, loss_out, (float*)dlogits);
-    else            hipLaunchKernelGGL(ce_rows_kernel<bf16>, dim3(B), dim3(256), 0, s, logits, target, K, ignore_index, cnt, loss_out, (bf16*)dlogits);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(ce_rows_kernel<T>, dim3(B), dim3(256), 0, s, logits, target, K, ignore_index, cnt, loss_out,
+                           static_cast<T*>(dlogits));
+    });
     ASSL_LAUNCH_CHECK();
 }
 

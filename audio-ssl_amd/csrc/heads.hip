@@ -764,15 +764,13 @@ extern "C" int audiossl_last_kernel(char* name, int capacity) {
     return ASSL_OK;
 }
 
-#define S_(stream) static_cast<hipStream_t>(stream)
-#define GRID1(n) dim3((unsigned)(((long)(n) + 255) / 256))
-
 extern "C" int audiossl_maxmean_fwd(int dtype, int out_f32, const void* H, void* y, uint8_t* arg, int N, int Tt, int D, void* stream) {
     ASSL_REQUIRE(H && y && arg && N > 0 && Tt > 0 && Tt < 256 && D > 0 && (D % 8) == 0 && (dtype == 0 || dtype == 1));
     const long total = (long)N * D / 8;
-    if (dtype == 0) hipLaunchKernelGGL((maxmean_fwd_kernel<float, float>), GRID1(total), dim3(256), 0, S_(stream), (const float*)H, (float*)y, arg, N, Tt, D);
-    else if (out_f32) hipLaunchKernelGGL((maxmean_fwd_kernel<bf16, float>), GRID1(total), dim3(256), 0, S_(stream), (const bf16*)H, (float*)y, arg, N, Tt, D);
-    else            hipLaunchKernelGGL((maxmean_fwd_kernel<bf16, bf16>), GRID1(total), dim3(256), 0, S_(stream), (const bf16*)H, (bf16*)y, arg, N, Tt, D);
+    assl_dispatch(dtype, [&](auto t, auto to) { using T = typename decltype(t)::type; using TO = typename decltype(to)::type;
+        hipLaunchKernelGGL((maxmean_fwd_kernel<T, TO>), GRID1(total), dim3(256), 0, S_(stream), static_cast<const T*>(H),
+                           static_cast<TO*>(y), arg, N, Tt, D);
+    }, out_f32 ? 0 : dtype);      // the output is the wide tensor here
     ASSL_LAUNCH_CHECK();
 }
 
@@ -781,9 +779,10 @@ extern "C" int audiossl_maxmean_bwd(int dtype, int gdtype, const void* dy, const
     ASSL_REQUIRE(dy && arg && H && dA && N > 0 && Tt > 0 && D > 0 && (D % 8) == 0 && (dtype == 0 || dtype == 1));
     ASSL_REQUIRE(gdtype == 0 || gdtype == dtype);
     const long total = (long)N * Tt * D / 8;
-    if (dtype == 0) hipLaunchKernelGGL((maxmean_bwd_kernel<float, float>), GRID1(total), dim3(256), 0, S_(stream), (const float*)dy, arg, (const float*)H, (float*)dA, N, Tt, D);
-    else if (gdtype == 0) hipLaunchKernelGGL((maxmean_bwd_kernel<bf16, float>), GRID1(total), dim3(256), 0, S_(stream), (const float*)dy, arg, (const bf16*)H, (bf16*)dA, N, Tt, D);
-    else            hipLaunchKernelGGL((maxmean_bwd_kernel<bf16, bf16>), GRID1(total), dim3(256), 0, S_(stream), (const bf16*)dy, arg, (const bf16*)H, (bf16*)dA, N, Tt, D);
+    assl_dispatch(dtype, [&](auto t, auto tg) { using T = typename decltype(t)::type; using TG = typename decltype(tg)::type;
+        hipLaunchKernelGGL((maxmean_bwd_kernel<T, TG>), GRID1(total), dim3(256), 0, S_(stream), static_cast<const TG*>(dy), arg,
+                           static_cast<const T*>(H), static_cast<T*>(dA), N, Tt, D);
+    }, gdtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -794,9 +793,10 @@ extern "C" int audiossl_colbn_fwd(int dtype, int adtype, const void* a, const fl
     ASSL_REQUIRE(a && scale && shift && h && groups > 0 && M > 0 && C > 0 && (C % 8) == 0 && (dtype == 0 || dtype == 1));
     ASSL_REQUIRE(adtype == 0 || adtype == dtype);
     const long total = groups * M * C / 8;
-    if (dtype == 0) hipLaunchKernelGGL((colbn_fwd_kernel<float, float>), GRID1(total), dim3(256), 0, S_(stream), (const float*)a, scale, shift, relu, (float*)h, M, C, groups);
-    else if (adtype == 0) hipLaunchKernelGGL((colbn_fwd_kernel<float, bf16>), GRID1(total), dim3(256), 0, S_(stream), (const float*)a, scale, shift, relu, (bf16*)h, M, C, groups);
-    else hipLaunchKernelGGL((colbn_fwd_kernel<bf16, bf16>), GRID1(total), dim3(256), 0, S_(stream), (const bf16*)a, scale, shift, relu, (bf16*)h, M, C, groups);
+    assl_dispatch(dtype, [&](auto to, auto ta) { using TO = typename decltype(to)::type; using TA = typename decltype(ta)::type;
+        hipLaunchKernelGGL((colbn_fwd_kernel<TA, TO>), GRID1(total), dim3(256), 0, S_(stream), static_cast<const TA*>(a), scale, shift,
+                           relu, static_cast<TO*>(h), M, C, groups);
+    }, adtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -810,18 +810,13 @@ extern "C" int audiossl_colbn_train_fwd(int dtype, int adtype, const void* a, co
     ASSL_REQUIRE(a && h && scale && shift && save_mean && save_rstd && groups > 0 && M > 0 && M <= 1024 && C > 0 && (C % 32) == 0);
     ASSL_REQUIRE((dtype == 0 || dtype == 1) && (adtype == 0 || adtype == dtype));
     ASSL_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-    hipStream_t s = S_(stream);
-#define TF(TA, TO) do {                                                                                                        \
-    if (M <= 512) hipLaunchKernelGGL((colbn_train_fwd_kernel<TA, TO, 8>), dim3(C / 32), dim3(256), 0, s, (const TA*)a, gamma, beta, \
-                                     running_mean, running_var, momentum, eps, relu, groups, (int)M, C, (TO*)h, scale, shift,    \
-                                     save_mean, save_rstd);                                                                     \
-    else hipLaunchKernelGGL((colbn_train_fwd_kernel<TA, TO, 16>), dim3(C / 32), dim3(256), 0, s, (const TA*)a, gamma, beta,      \
-                            running_mean, running_var, momentum, eps, relu, groups, (int)M, C, (TO*)h, scale, shift, save_mean,  \
-                            save_rstd); } while (0)
-    if (dtype == 0) TF(float, float);
-    else if (adtype == 0) TF(float, bf16);
-    else TF(bf16, bf16);
-#undef TF
+    assl_dispatch(dtype, [&](auto to, auto ta) { using TO = typename decltype(to)::type; using TA = typename decltype(ta)::type;
+        assl_rows(M, [&](auto nr) {
+            hipLaunchKernelGGL((colbn_train_fwd_kernel<TA, TO, nr()>), dim3(C / 32), dim3(256), 0, S_(stream), static_cast<const TA*>(a), gamma,
+                               beta, running_mean, running_var, momentum, eps, relu, groups, (int)M, C, static_cast<TO*>(h), scale,
+                               shift, save_mean, save_rstd);
+        });
+    }, adtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -836,17 +831,14 @@ extern "C" int audiossl_colbn_bwd(int dtype, int adtype, int gdtype, const void*
     static const bool fused_ok = getenv("AUDIOSSL_BN_FUSED") ? atoi(getenv("AUDIOSSL_BN_FUSED")) != 0 : true;
     if (fused_ok && M <= 1024 && (C % 32) == 0) {             // short batches: statistics + apply in one launch
         dim3 fgrid(C / 32, groups);
-#define CF(TA, TG, TO) do {                                                                                                    \
-    if (M <= 512) hipLaunchKernelGGL((colbn_bwd_fused_kernel<TA, TG, TO, 8>), fgrid, dim3(256), 0, s, (const TA*)a, (const TG*)dh, \
-                                     scale, shift, mean, rstd, relu, (int)M, C, (TO*)da, dgamma, dbeta);                        \
-    else hipLaunchKernelGGL((colbn_bwd_fused_kernel<TA, TG, TO, 16>), fgrid, dim3(256), 0, s, (const TA*)a, (const TG*)dh,      \
-                            scale, shift, mean, rstd, relu, (int)M, C, (TO*)da, dgamma, dbeta); } while (0)
-        if (dtype == 0) CF(float, float, float);
-        else if (adtype == 0 && gdtype == 0) CF(float, float, bf16);
-        else if (adtype == 0) CF(float, bf16, bf16);
-        else if (gdtype == 0) CF(bf16, float, bf16);
-        else CF(bf16, bf16, bf16);
-#undef CF
+        assl_dispatch(dtype, [&](auto to, auto ta, auto tg) {
+            using TO = typename decltype(to)::type; using TA = typename decltype(ta)::type; using TG = typename decltype(tg)::type;
+            assl_rows(M, [&](auto nr) {
+                hipLaunchKernelGGL((colbn_bwd_fused_kernel<TA, TG, TO, nr()>), fgrid, dim3(256), 0, s, static_cast<const TA*>(a),
+                                   static_cast<const TG*>(dh), scale, shift, mean, rstd, relu, (int)M, C, static_cast<TO*>(da), dgamma,
+                                   dbeta);
+            });
+        }, adtype, gdtype);
         ASSL_LAUNCH_CHECK();
     }
     ASSL_ZERO(tmp, sizeof(double) * 2 * C * groups, s);
@@ -854,17 +846,15 @@ extern "C" int audiossl_colbn_bwd(int dtype, int adtype, int gdtype, const void*
     dim3 grid(ceil_div(M, rpb), C / 64, groups);
     const long total = groups * M * C / 8;
     const long GC = (long)groups * C;
-#define CB(TA, TG, TO) do {                                                                                                           \
-    hipLaunchKernelGGL((colbn_bwd_stats_kernel<TA, TG>), grid, dim3(256), 0, s, (const TA*)a, (const TG*)dh, scale, shift, mean, rstd,  \
-                       relu, M, C, rpb, tmp, tmp + GC);                                                                               \
-    hipLaunchKernelGGL((colbn_bwd_apply_kernel<TA, TG, TO>), GRID1(total), dim3(256), 0, s, (const TA*)a, (const TG*)dh, scale, shift,  \
-                       mean, rstd, relu, M, C, groups, tmp, tmp + GC, (TO*)da, dgamma, dbeta, 1.f / (float)M); } while (0)
-    if (dtype == 0) CB(float, float, float);
-    else if (adtype == 0 && gdtype == 0) CB(float, float, bf16);
-    else if (adtype == 0) CB(float, bf16, bf16);
-    else if (gdtype == 0) CB(bf16, float, bf16);
-    else CB(bf16, bf16, bf16);
-#undef CB
+    assl_dispatch(dtype, [&](auto to, auto ta, auto tg) {
+        using TO = typename decltype(to)::type; using TA = typename decltype(ta)::type; using TG = typename decltype(tg)::type;
+        const TA* at = static_cast<const TA*>(a);
+        const TG* g = static_cast<const TG*>(dh);
+        hipLaunchKernelGGL((colbn_bwd_stats_kernel<TA, TG>), grid, dim3(256), 0, s, at, g, scale, shift, mean, rstd, relu, M, C, rpb,
+                           tmp, tmp + GC);
+        hipLaunchKernelGGL((colbn_bwd_apply_kernel<TA, TG, TO>), GRID1(total), dim3(256), 0, s, at, g, scale, shift, mean, rstd, relu,
+                           M, C, groups, tmp, tmp + GC, static_cast<TO*>(da), dgamma, dbeta, 1.f / (float)M);
+    }, adtype, gdtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -881,13 +871,10 @@ extern "C" int audiossl_colbn_bwd_stats(int dtype, int adtype, int gdtype, const
     const int rpb = M >= 4096 ? 256 : 64;
     dim3 grid(ceil_div(M, rpb), C / 64, groups);
     const long GC = (long)groups * C;
-#define CS(TA, TG) hipLaunchKernelGGL((colbn_bwd_stats_kernel<TA, TG>), grid, dim3(256), 0, s, (const TA*)a, (const TG*)dh, scale, shift, \
-                                      mean, rstd, relu, M, C, rpb, tmp, tmp + GC)
-    if (dtype == 0 || (adtype == 0 && gdtype == 0)) CS(float, float);
-    else if (adtype == 0) CS(float, bf16);
-    else if (gdtype == 0) CS(bf16, float);
-    else CS(bf16, bf16);
-#undef CS
+    assl_dispatch(dtype, [&](auto, auto ta, auto tg) { using TA = typename decltype(ta)::type; using TG = typename decltype(tg)::type;
+        hipLaunchKernelGGL((colbn_bwd_stats_kernel<TA, TG>), grid, dim3(256), 0, s, static_cast<const TA*>(a),
+                           static_cast<const TG*>(dh), scale, shift, mean, rstd, relu, M, C, rpb, tmp, tmp + GC);
+    }, adtype, gdtype);      // no output of the path's type: two tuples share <float, float>
     ASSL_LAUNCH_CHECK();
 }
 extern "C" int audiossl_colbn_bwd_apply(int dtype, int adtype, int gdtype, const void* a, const void* dh, const float* scale,
@@ -895,19 +882,15 @@ extern "C" int audiossl_colbn_bwd_apply(int dtype, int adtype, int gdtype, const
                                         const double* sums, double count, void* da, void* stream) {
     ASSL_REQUIRE(a && dh && scale && shift && mean && rstd && sums && da && groups > 0 && M > 0 && C > 0 && (C % 64) == 0 && count > 1.0);
     ASSL_REQUIRE((dtype == 0 || dtype == 1) && (gdtype == 0 || gdtype == dtype) && (adtype == 0 || adtype == dtype));
-    hipStream_t s = S_(stream);
     const long total = groups * M * C / 8;
     const long GC = (long)groups * C;
     const float inv = (float)(1.0 / count);
-#define CA(TA, TG, TO) hipLaunchKernelGGL((colbn_bwd_apply_kernel<TA, TG, TO>), GRID1(total), dim3(256), 0, s, (const TA*)a, (const TG*)dh, \
-                                          scale, shift, mean, rstd, relu, M, C, groups, sums, sums + GC, (TO*)da, (float*)nullptr,          \
-                                          (float*)nullptr, inv)
-    if (dtype == 0) CA(float, float, float);
-    else if (adtype == 0 && gdtype == 0) CA(float, float, bf16);
-    else if (adtype == 0) CA(float, bf16, bf16);
-    else if (gdtype == 0) CA(bf16, float, bf16);
-    else CA(bf16, bf16, bf16);
-#undef CA
+    assl_dispatch(dtype, [&](auto to, auto ta, auto tg) {
+        using TO = typename decltype(to)::type; using TA = typename decltype(ta)::type; using TG = typename decltype(tg)::type;
+        hipLaunchKernelGGL((colbn_bwd_apply_kernel<TA, TG, TO>), GRID1(total), dim3(256), 0, S_(stream), static_cast<const TA*>(a),
+                           static_cast<const TG*>(dh), scale, shift, mean, rstd, relu, M, C, groups, sums, sums + GC,
+                           static_cast<TO*>(da), (float*)nullptr, (float*)nullptr, inv);
+    }, adtype, gdtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -927,13 +910,13 @@ extern "C" int audiossl_colbn_train_fwd_multi(int count, int adtype, const void*
         m.rm[p] = running_mean ? running_mean[p] : nullptr; m.rv[p] = running_var ? running_var[p] : nullptr;
         ASSL_REQUIRE((m.rm[p] == nullptr) == (m.rv[p] == nullptr));
     }
-    hipStream_t s = S_(stream);
     dim3 grid(C / 32, count);
-#define TFM(TA, NR_) hipLaunchKernelGGL((colbn_train_fwd_multi_kernel<TA, bf16, NR_>), grid, dim3(256), 0, s, m, momentum, eps, relu, \
-                                        groups, (int)M, C)
-    if (adtype == 0) { if (M <= 512) TFM(float, 8); else TFM(float, 16); }
-    else             { if (M <= 512) TFM(bf16, 8); else TFM(bf16, 16); }
-#undef TFM
+    assl_dispatch(1, [&](auto, auto ta) { using TA = typename decltype(ta)::type;
+        assl_rows(M, [&](auto nr) {
+            hipLaunchKernelGGL((colbn_train_fwd_multi_kernel<TA, bf16, nr()>), grid, dim3(256), 0, S_(stream), m, momentum, eps, relu, groups,
+                               (int)M, C);
+        });
+    }, adtype);      // the output is bf16 always
     ASSL_LAUNCH_CHECK();
 }
 
@@ -949,16 +932,12 @@ extern "C" int audiossl_colbn_bwd_multi(int count, int adtype, int gdtype, const
         m.dgamma[p] = dgamma ? dgamma[p] : nullptr; m.dbeta[p] = dbeta ? dbeta[p] : nullptr;
         ASSL_REQUIRE((m.dgamma[p] == nullptr) == (m.dbeta[p] == nullptr));
     }
-    hipStream_t s = S_(stream);
     dim3 grid(C / 32, groups, count);
-#define BWM(TA, TG, NR_) hipLaunchKernelGGL((colbn_bwd_multi_kernel<TA, TG, bf16, NR_>), grid, dim3(256), 0, s, m, relu, groups, (int)M, C)
-#define BWM2(TA, TG) do { if (M <= 512) BWM(TA, TG, 8); else BWM(TA, TG, 16); } while (0)
-    if (adtype == 0 && gdtype == 0) BWM2(float, float);
-    else if (adtype == 0) BWM2(float, bf16);
-    else if (gdtype == 0) BWM2(bf16, float);
-    else BWM2(bf16, bf16);
-#undef BWM2
-#undef BWM
+    assl_dispatch(1, [&](auto, auto ta, auto tg) { using TA = typename decltype(ta)::type; using TG = typename decltype(tg)::type;
+        assl_rows(M, [&](auto nr) {
+            hipLaunchKernelGGL((colbn_bwd_multi_kernel<TA, TG, bf16, nr()>), grid, dim3(256), 0, S_(stream), m, relu, groups, (int)M, C);
+        });
+    }, adtype, gdtype);
     ASSL_LAUNCH_CHECK();
 }
 
@@ -987,25 +966,27 @@ extern "C" int audiossl_barlow_loss(int dtype, const float* c, int D, float coef
     ASSL_REQUIRE(c && dc && loss_out && D > 0 && (D % 8) == 0 && D <= 16384 && (dtype == 0 || dtype == 1));
     if (!ASSL_ALIGNED16(c) || !ASSL_ALIGNED16(dc)) return ASSL_EALIGN;
     const int grid = min(512, ceil_div((long)D * (D / 8), 256));
-    if (dtype == 0) hipLaunchKernelGGL(barlow_loss_kernel<float>, dim3(grid), dim3(256), 0, S_(stream), c, D, coef, dscale, (float*)dc, loss_out);
-    else            hipLaunchKernelGGL(barlow_loss_kernel<bf16>, dim3(grid), dim3(256), 0, S_(stream), c, D, coef, dscale, (bf16*)dc, loss_out);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(barlow_loss_kernel<T>, dim3(grid), dim3(256), 0, S_(stream), c, D, coef, dscale, static_cast<T*>(dc), loss_out);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_l2norm_fwd(int dtype, const float* q, int B, int D, void* qn, float* qn32, float* inv_norm, void* stream) {
     ASSL_REQUIRE(q && qn && qn32 && inv_norm && B > 0 && D > 0 && (dtype == 0 || dtype == 1));
-    if (dtype == 0) hipLaunchKernelGGL(l2norm_fwd_kernel<float>, dim3(B), dim3(64), 0, S_(stream), q, D, (float*)qn, qn32, inv_norm);
-    else            hipLaunchKernelGGL(l2norm_fwd_kernel<bf16>, dim3(B), dim3(64), 0, S_(stream), q, D, (bf16*)qn, qn32, inv_norm);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(l2norm_fwd_kernel<T>, dim3(B), dim3(64), 0, S_(stream), q, D, static_cast<T*>(qn), qn32, inv_norm);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_moco_prep(int dtype, const float* q, const float* k, int B, int D, float scale, void* qn, float* qn32, float* qinv,
                                   void* kn, float* kn32, float* kinv, float* lpos, void* stream) {
     ASSL_REQUIRE(q && k && qn && qn32 && qinv && kn && kn32 && kinv && lpos && B > 0 && D > 0 && (dtype == 0 || dtype == 1));
-    if (dtype == 0) hipLaunchKernelGGL(moco_prep_kernel<float>, dim3(B), dim3(64), 0, S_(stream), q, k, D, scale, (float*)qn, qn32, qinv,
-                                       (float*)kn, kn32, kinv, lpos);
-    else            hipLaunchKernelGGL(moco_prep_kernel<bf16>, dim3(B), dim3(64), 0, S_(stream), q, k, D, scale, (bf16*)qn, qn32, qinv,
-                                       (bf16*)kn, kn32, kinv, lpos);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(moco_prep_kernel<T>, dim3(B), dim3(64), 0, S_(stream), q, k, D, scale, static_cast<T*>(qn), qn32, qinv,
+                           static_cast<T*>(kn), kn32, kinv, lpos);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -1033,16 +1014,18 @@ extern "C" int audiossl_moco_ce_bwd(int dtype, const float* lpos, const float* l
                                     void* P, float* dlpos, void* stream) {
     ASSL_REQUIRE(lpos && lneg && lse && P && dlpos && B > 0 && K > 0 && (dtype == 0 || dtype == 1));
     dim3 grid(ceil_div(K, 256 * 8), B);
-    if (dtype == 0) hipLaunchKernelGGL(moco_ce_bwd_kernel<float>, grid, dim3(256), 0, S_(stream), lpos, lneg, lse, K, gscale, (float*)P, dlpos);
-    else            hipLaunchKernelGGL(moco_ce_bwd_kernel<bf16>, grid, dim3(256), 0, S_(stream), lpos, lneg, lse, K, gscale, (bf16*)P, dlpos);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(moco_ce_bwd_kernel<T>, grid, dim3(256), 0, S_(stream), lpos, lneg, lse, K, gscale, static_cast<T*>(P), dlpos);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_l2norm_bwd(int dtype, const float* dqn, const float* dlpos, const float* kn32, const float* qn32,
                                    const float* inv_norm, int B, int D, void* dq, void* stream) {
     ASSL_REQUIRE(dqn && dlpos && kn32 && qn32 && inv_norm && dq && B > 0 && D > 0 && (dtype == 0 || dtype == 1));
-    if (dtype == 0) hipLaunchKernelGGL(l2norm_bwd_kernel<float>, dim3(B), dim3(64), 0, S_(stream), dqn, dlpos, kn32, qn32, inv_norm, D, (float*)dq);
-    else            hipLaunchKernelGGL(l2norm_bwd_kernel<bf16>, dim3(B), dim3(64), 0, S_(stream), dqn, dlpos, kn32, qn32, inv_norm, D, (bf16*)dq);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(l2norm_bwd_kernel<T>, dim3(B), dim3(64), 0, S_(stream), dqn, dlpos, kn32, qn32, inv_norm, D, static_cast<T*>(dq));
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -1051,8 +1034,9 @@ extern "C" int audiossl_enqueue(int dtype, const float* keys, int B, int D, int 
     ASSL_REQUIRE(keys && queue && B > 0 && D > 0 && K > 0 && B <= K && (dtype == 0 || dtype == 1));
     ASSL_REQUIRE(ptr_dev || (ptr >= 0 && ptr + B <= K));
     const int grid = ceil_div((long)B * D, 256);
-    if (dtype == 0) hipLaunchKernelGGL(enqueue_kernel<float>, dim3(grid), dim3(256), 0, S_(stream), keys, B, D, K, ptr, ptr_dev, queue, (float*)shadow);
-    else            hipLaunchKernelGGL(enqueue_kernel<bf16>, dim3(grid), dim3(256), 0, S_(stream), keys, B, D, K, ptr, ptr_dev, queue, (bf16*)shadow);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(enqueue_kernel<T>, dim3(grid), dim3(256), 0, S_(stream), keys, B, D, K, ptr, ptr_dev, queue, static_cast<T*>(shadow));
+    });
     if (ptr_dev) hipLaunchKernelGGL(advance_ptr_kernel, dim3(1), dim3(1), 0, S_(stream), ptr_dev, B, K);
     ASSL_LAUNCH_CHECK();
 }
@@ -1099,16 +1083,18 @@ extern "C" int audiossl_cast(int dtype, const float* src, void* dst, long n, voi
     ASSL_REQUIRE(src && dst && n > 0 && (dtype == 0 || dtype == 1));
     const int grid = (int)min((long)4096, (n / 8 + 255) / 256 + 1);
     const int vec = ASSL_ALIGNED16(src) && ASSL_ALIGNED16(dst);
-    if (dtype == 0) hipLaunchKernelGGL(cast_kernel<float>, dim3(grid), dim3(256), 0, S_(stream), src, (float*)dst, n, vec);
-    else            hipLaunchKernelGGL(cast_kernel<bf16>, dim3(grid), dim3(256), 0, S_(stream), src, (bf16*)dst, n, vec);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(cast_kernel<T>, dim3(grid), dim3(256), 0, S_(stream), src, static_cast<T*>(dst), n, vec);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
 extern "C" int audiossl_cast_back(int dtype, const void* src, float* dst, long n, void* stream) {
     ASSL_REQUIRE(src && dst && n > 0 && (dtype == 0 || dtype == 1));
     const int grid = (int)min((long)4096, (n + 255) / 256);
-    if (dtype == 0) hipLaunchKernelGGL(cast_back_kernel<float>, dim3(grid), dim3(256), 0, S_(stream), (const float*)src, dst, n);
-    else            hipLaunchKernelGGL(cast_back_kernel<bf16>, dim3(grid), dim3(256), 0, S_(stream), (const bf16*)src, dst, n);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(cast_back_kernel<T>, dim3(grid), dim3(256), 0, S_(stream), static_cast<const T*>(src), dst, n);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -1256,8 +1242,10 @@ __global__ void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, 
 
 extern "C" int audiossl_relu_bwd(int dtype, const void* g, const void* h, void* out, long n, void* stream) {
     ASSL_REQUIRE(g && h && out && n > 0 && (n % 8) == 0 && (dtype == 0 || dtype == 1));
-    if (dtype == 0) hipLaunchKernelGGL(relu_bwd_kernel<float>, GRID1(n / 8), dim3(256), 0, S_(stream), (const float*)g, (const float*)h, (float*)out, n / 8);
-    else            hipLaunchKernelGGL(relu_bwd_kernel<bf16>, GRID1(n / 8), dim3(256), 0, S_(stream), (const bf16*)g, (const bf16*)h, (bf16*)out, n / 8);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(relu_bwd_kernel<T>, GRID1(n / 8), dim3(256), 0, S_(stream), static_cast<const T*>(g), static_cast<const T*>(h),
+                           static_cast<T*>(out), n / 8);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -1280,8 +1268,9 @@ extern "C" int audiossl_center_cast(const float* y, void* yc, float* cmean, int 
     ASSL_REQUIRE(y && yc && cmean && groups > 0 && M > 0 && M <= 1024 && C > 0 && C % 32 == 0);
     ASSL_REQUIRE(ASSL_ALIGNED16(y) && ASSL_ALIGNED16(yc));
     const dim3 grid(C / 32, groups);
-    if (M <= 512) hipLaunchKernelGGL(center_cast_kernel<8>, grid, dim3(256), 0, S_(stream), y, (bf16*)yc, cmean, (int)M, C);
-    else          hipLaunchKernelGGL(center_cast_kernel<16>, grid, dim3(256), 0, S_(stream), y, (bf16*)yc, cmean, (int)M, C);
+    assl_rows(M, [&](auto nr) {
+        hipLaunchKernelGGL(center_cast_kernel<nr()>, grid, dim3(256), 0, S_(stream), y, static_cast<bf16*>(yc), cmean, (int)M, C);
+    });
     ASSL_LAUNCH_CHECK();
 }
 
@@ -1296,8 +1285,7 @@ extern "C" int audiossl_center_cast_multi(int count, const float* const* y, void
         cmax = max(cmax, C[i]);
     }
     const dim3 grid(cmax / 32, groups, count);
-    if (M <= 512) hipLaunchKernelGGL(center_cast_multi_kernel<8>, grid, dim3(256), 0, S_(stream), m, (int)M);
-    else          hipLaunchKernelGGL(center_cast_multi_kernel<16>, grid, dim3(256), 0, S_(stream), m, (int)M);
+    assl_rows(M, [&](auto nr) { hipLaunchKernelGGL(center_cast_multi_kernel<nr()>, grid, dim3(256), 0, S_(stream), m, (int)M); });
     ASSL_LAUNCH_CHECK();
 }
 

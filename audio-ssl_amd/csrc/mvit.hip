@@ -458,8 +458,6 @@ __global__ __launch_bounds__(256) void tokpool_max_bwd_kernel(const float* __res
 
 }  // namespace
 
-#define S_(stream) static_cast<hipStream_t>(stream)
-
 static bool pool_shape_ok(int B, int heads, int d, int H, int W, int Ho, int Wo, int sh, int sw, bool pooled) {
     if (B <= 0 || heads <= 0 || d <= 0 || d > MAXD || H <= 0 || W <= 0 || sh <= 0 || sw <= 0) return false;
     if (!pooled) return Ho == H && Wo == W;

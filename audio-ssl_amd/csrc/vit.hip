@@ -330,8 +330,6 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 
 }  // namespace
 
-#define S_(stream) static_cast<hipStream_t>(stream)
-
 extern "C" int audiossl_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, float* y32, float* mean, float* rstd,
                                       int M, int C, float eps, void* stream) {
     ASSL_REQUIRE(x && gamma && beta && y && mean && rstd && M > 0 && C > 0 && C <= 64 * LN_MAX);

@@ -499,8 +499,9 @@ STEM_SALT = 100              # salt of the image: at both shapes it leaves every
 
 
 @functools.lru_cache(maxsize=None)
-def stem_ref(shape, round_bf16=False):
-    """fp64 autograd through Conv2d(1,64,3,p=1) -> BatchNorm2d(train) -> ReLU -> MaxPool2d(2) and the mean over pooled time"""
+def stem_ref(shape, round_bf16=False, gdtype=0):
+    """fp64 autograd through Conv2d(1,64,3,p=1) -> BatchNorm2d(train) -> ReLU -> MaxPool2d(2) and the mean over pooled time;
+    gdtype 1: the incoming gradients as a bf16 caller stores them"""
     import torch.nn as nn
     Nimg, F_, T = shape
     To, Fo = T // 2, F_ // 2
@@ -513,6 +514,8 @@ def stem_ref(shape, round_bf16=False):
     gamma, beta = bn.weight.detach().clone(), bn.bias.detach().clone()
     gP = torch.from_numpy(fill.uniform((Nimg, 64, Fo, To), 42))
     gX1 = torch.from_numpy(fill.uniform((Nimg, Fo * 64), 43))
+    if gdtype == 1:
+        gP, gX1 = gP.bfloat16().float(), gX1.bfloat16().float()
     xin = (x.bfloat16().float() if round_bf16 else x).double()
     w = (w32.bfloat16().float() if round_bf16 else w32).double().requires_grad_(True)
     ga, be = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)

@@ -194,3 +194,38 @@ def test_partial_gradient_clear_table_and_flags():
     fg.zero_grad()
     assert float(fg.grad.min()) == 1.0 and fg._fresh_grad is False  # a full fused clear buys one skipped sweep, as before
 
+
+
+DISPATCH_TABLE = """\
+d 0 F
+d 0 0 FF
+d 0 0 0 FFF
+d 1 B
+d 1 0 BF
+d 1 0 0 BFF
+d 1 0 1 BFB
+d 1 1 BB
+d 1 1 0 BBF
+d 1 1 1 BBB
+r 1 8
+r 512 8
+r 513 16
+r 1024 16
+i 2 3 5
+"""
+
+
+def test_dtype_dispatch_hands_out_the_legal_tags_and_no_others(tmp_path):
+    """csrc/dispatch.h, stand-alone under the address and undefined-behaviour sanitizers: "d <dtype> [<wide code> ...] <tags>"
+    per legal code tuple (F = float, B = bf16; the three-code rows are dtype / ydtype / gdtype of the BatchNorm backward),
+    "r <M> <NR>" for the row split, and "i" = the number of lambda instantiations for one, two and three tags (1 + 2^n)."""
+    import subprocess
+
+    import build as B
+    exe = str(tmp_path / "dispatch_check")
+    cxx = os.path.join(os.path.dirname(B.HIPCC), "amdclang++")          # the host compiler next to hipcc
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", B.CSRC,
+                    os.path.join(os.path.dirname(__file__), "dispatch_check.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr
+    assert run.stdout == DISPATCH_TABLE
