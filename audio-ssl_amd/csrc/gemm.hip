@@ -1381,6 +1381,8 @@ Tiles count_tiles(const Problem& p) {
 }
 
 // Where a variant may run at all, bf16 operands (the choice functions add where it is measured to win; AUDIOSSL_GEMM_FORCE needs only this).
+// tests/gemm_cases.py restates this function (legal()) to generate only cases the forced variant takes: change both together, or the
+// kernel-name assertions of tests/test_gpu_gemm_matrix.py turn red.
 bool legal(Variant v, const Problem& p, const Tiles& t) {
     // the hand-scheduled kernels: K % 64, whole 16-byte rows, at least one full tile of the smallest shape
     bool hs_ok = p.M >= 128 && p.N >= 128 && (!p.ta || p.M % 8 == 0);

@@ -260,6 +260,9 @@ int audiossl_conv3x3_wgrad(const void* dY, const void* X, float* dWp, float* wor
  * C[M,N] (+)= alpha * op(A) * op(B), operands of `dtype`, fp32 accumulate.
  *   trans_a = 0: A is [M][K] (lda)   trans_a = 1: A is [K][M] (lda)
  *   trans_b = 0: B is [N][K] (ldb)   trans_b = 1: B is [K][N] (ldb)     (torch Linear weights are [N][K])
+ * The two flags are independent: all four (trans_a, trans_b) combinations are supported by every kernel variant and tested
+ * (tests/test_gpu_gemm_matrix.py).  The contiguous dimension of an operand is a multiple of 8, so N % 8 == 0 is required only for
+ * trans_b = 1 (M % 8 == 0 only for trans_a = 1, K % 8 == 0 unless both are set); lda / ldb are multiples of 8 and may exceed the width.
  * Epilogue, in order: + bias[N]; ReLU; * keep[M][ldk] * keep_scale (dropout); zero where gate[M][ldg] <= 0;
  * + resid[M][ldr] (fp32, out-of-place residual connection of the transformer blocks; ksplit 1, not atomic);
  * store as dtype, or fp32 (out_f32), or accumulate into fp32 C: atomic = 1 by atomicAdd (required when ksplit > 1 or when
