@@ -140,12 +140,22 @@ class BaseDataset(Dataset):
         self.to_mel_spec = MelSpectrogramLibrosa() if per_sample else None
         if self.config["pretrain"]["input"]["type"] != "raw_wav":
             raise NotImplementedError("only input.type == raw_wav is supported (SURVEY 2.4)")
+        # UnFuSeD trains on pseudo-labels (`extras/unfused/dataset.py`: the `label` column next to `files`)
+        self.labelled = self.upstream == "unfused"
+        if self.labelled and "label" not in self.data.columns:
+            raise ValueError(f"--upstream unfused needs a `label` column in {data_csv} (a `files,label` CSV); "
+                             f"found columns {list(self.data.columns)}")
 
     @property
     def unit_length(self):
         return int(self.length * 16000)
 
     def __getitem__(self, idx):
+        if self.labelled:
+            return self._clip(idx), int(self.data["label"][idx])
+        return self._clip(idx)
+
+    def _clip(self, idx):
         wave = load_audio(self.data["files"][idx], self.sampling_rate, raw=self.pcm)
         if isinstance(wave, NativeRate):
             return wave                      # resampled on the GPU by the main-process collate
@@ -173,12 +183,20 @@ class WindowCollate:
     The python `random` stream is consumed exactly as the reference's sequential loader would (per clip: the window
     start, then that clip's view parameters), so crops and augmentation indices are bit-identical to a reference run
     with `num_workers=0`.  pcm=True: the same draws and plan, and the windows leave as a `PcmBatch` (`PcmClip`s in their own
-    sample formats, resampled clips as float32) in place of the zero-padded float32 tensor."""
+    sample formats, resampled clips as float32) in place of the zero-padded float32 tensor.
+    A batch of `(clip, label)` pairs (`--upstream unfused`) gives the same two elements plus the labels as a CPU int64 tensor in
+    batch order; the labels draw nothing from the random streams."""
 
     def __init__(self, tfms, unit_length, n_mels, hop=160, pcm=False):
         self.tfms, self.unit, self.n_mels, self.hop, self.pcm = tfms, unit_length, n_mels, hop, pcm
 
     def __call__(self, waves):
+        if len(waves) and isinstance(waves[0], tuple):
+            labels = torch.tensor([int(y) for _, y in waves], dtype=torch.int64)
+            return self._collate([w for w, _ in waves]) + (labels,)
+        return self._collate(waves)
+
+    def _collate(self, waves):
         from src.dataset import ingest
         waves = [ingest.resample(torch.from_numpy(w.data), w.rate, AUDIO_SR).cpu() if isinstance(w, NativeRate) else w for w in waves]
         B = len(waves)
@@ -245,5 +263,5 @@ class _CollatedLoader:
 
     def __iter__(self):
         for items in self.loader:
-            waves, plan = self.collate(items)
-            yield waves.pin_memory() if torch.cuda.is_available() else waves, plan
+            waves, plan, *labels = self.collate(items)
+            yield (waves.pin_memory() if torch.cuda.is_available() else waves, plan, *labels)

@@ -643,10 +643,11 @@ class ProjCtx:
     pass
 
 
-def projector_forward(PP, Y, dtype, groups, B, update_running=True, Wc=None):
+def projector_forward(PP, Y, dtype, groups, B, update_running=True, Wc=None, final_bn=True):
     """Lin-BN-ReLU-Lin-BN-ReLU-Lin then affine-free BN on `groups` stacked batches Y [groups*B, in] (the two views share
     the weights, so they go through each GEMM together; BatchNorm statistics stay per view).
-    PP keys: projector.{0,3,6}.weight, projector.{1,4}.{weight,bias,running_mean,running_var}, bn.{running_*}."""
+    PP keys: projector.{0,3,6}.weight, projector.{1,4}.{weight,bias,running_mean,running_var}, bn.{running_*}.
+    final_bn=False: the chain ends at the third Linear (UnFuSeD's `Project`); its output z is returned as fp32 logits."""
     kin = Y.shape[1]
     c = ProjCtx()
     c.dtype, c.B, c.groups, c.kin, c.y = dtype, B, groups, kin, Y
@@ -694,6 +695,10 @@ def projector_forward(PP, Y, dtype, groups, B, update_running=True, Wc=None):
     c.a2 = linear_fwd(dtype, c.h1, W[1], M, D, D, out_f32=o32)
     c.h2 = _empty((M, D), td, like=Y)
     c.st2 = bn(c.a2, "projector.4", True, 1, c.h2)
+    c.final_bn = final_bn
+    if not final_bn:
+        c.z = linear_fwd(dtype, c.h2, W[2], M, D, D, out_f32=1)
+        return c.z, c
     c.z = linear_fwd(dtype, c.h2, W[2], M, D, D, out_f32=o32)
     c.zn = _empty((M, D), td, like=Y)
     c.st0 = bn(c.z, "bn", False, 0, c.zn)
@@ -701,8 +706,9 @@ def projector_forward(PP, Y, dtype, groups, B, update_running=True, Wc=None):
 
 
 def projector_backward(c, PP, G, dzn, dy_rows=None):
-    """dzn [groups*B, D] (activation dtype) -> accumulates projector grads into G; returns dY for the first `dy_rows`
-    rows of the stacked input (None: all rows, 0: skip)."""
+    """dzn [groups*B, D] (fp32) -> accumulates projector grads into G; returns dY for the first `dy_rows`
+    rows of the stacked input (None: all rows, 0: skip).  A forward with final_bn=False takes the gradient of its logits
+    (activation dtype) in place of dzn."""
     dtype, B, D, kin, groups = c.dtype, c.B, c.D, c.kin, c.groups
     M = groups * B
     td = N.torch_dtype(dtype)
@@ -724,17 +730,20 @@ def projector_backward(c, PP, G, dzn, dy_rows=None):
             for g in range(groups):              # t = [dbeta sums: groups x D][dgamma sums: groups x D]
                 N.call("add_d2f", t[g * D:(g + 1) * D], g_beta, D)
                 N.call("add_d2f", t[(groups + g) * D:(groups + g + 1) * D], g_gamma, D)
-    dz = _empty((M, D), td, like=c.zn)
     # gradients entering a BatchNorm backward (dzn, dh2, dh1) are fp32 GEMM outputs; its outputs (dz, da2, da1) are
     # MFMA operands only and are stored in the activation dtype
-    bn_bwd(c.z, dzn, c.st0, 0, dz, None, None)
+    if c.final_bn:
+        dz = _empty((M, D), td, like=c.zn)
+        bn_bwd(c.z, dzn, c.st0, 0, dz, None, None)
+    else:
+        dz = dzn
     linear_bwd_w(dtype, dz, c.h2, G["projector.6.weight"], M, D, D)
     dh2 = linear_bwd_x(dtype, dz, c.W[2], M, D, D, out_f32=1)
-    da2 = _empty((M, D), td, like=c.zn)
+    da2 = _empty((M, D), td, like=dz)
     bn_bwd(c.a2, dh2, c.st2, 1, da2, G["projector.4.weight"], G["projector.4.bias"])
     linear_bwd_w(dtype, da2, c.h1, G["projector.3.weight"], M, D, D)
     dh1 = linear_bwd_x(dtype, da2, c.W[1], M, D, D, out_f32=1)
-    da1 = _empty((M, D), td, like=c.zn)
+    da1 = _empty((M, D), td, like=dz)
     bn_bwd(c.a1, dh1, c.st1, 1, da1, G["projector.1.weight"], G["projector.1.bias"], adt=c.ad1)
     linear_bwd_w(dtype, da1, c.y_hi, G["projector.0.weight"], M, D, kin)
     if c.y_lo is not None:

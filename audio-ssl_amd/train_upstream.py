@@ -109,15 +109,18 @@ class HipTrainer:
             while nxt is not None:
                 i += 1
                 waves = nxt[0]
+                labels = nxt[2] if len(nxt) > 2 else None      # this batch's labels: `nxt` is about to become the next batch
                 img_1, img_2 = dm.front_end.collect(ticket)
                 nxt = next(batches, None)               # the next batch's log-mel + augmentation runs under this step
                 if nxt is not None:
                     ticket = dm.front_end.submit(nxt[0].to(dev, non_blocking=True), nxt[1])
+                if labels is not None and gstep is not None:
+                    model.set_labels(labels)                    # a labelled batch (unfused): into the expert's fixed device buffer
                 if gstep is not None:
                     loss = gstep(img_1, img_2)
                 else:
                     opt.zero_grad()
-                    loss = model.training_step((img_1, img_2), i)
+                    loss = model.training_step((img_1, img_2) if labels is None else ((img_1, img_2), labels), i)
                     loss.backward()
                     model.all_reduce_grads()
                     opt.step()
@@ -185,7 +188,7 @@ def main(args):
 
 def get_args(argv=None):
     parser = argparse.ArgumentParser(allow_abbrev=False)
-    parser.add_argument("--input", help="csv with a `files` column", type=str, required=True)
+    parser.add_argument("--input", help="csv with a `files` column (and a `label` column for --upstream unfused)", type=str, required=True)
     parser.add_argument('--load_checkpoint', type=str, help='load checkpoint', default=None)
     parser.add_argument('-c', '--config', metavar='CONFIG_PATH', help='yaml config of the whole experiment', default=None)
     parser.add_argument('--upstream', type=str, help='define the type of upstream', default='delores_m')

@@ -442,6 +442,19 @@ int audiossl_row_sqnorm(const float* x, int rows, int D, float scale, float* out
 int audiossl_ce_rows(int dtype, const float* logits, const long long* target, int B, int K, int ignore_index, int* cnt,
                      float* loss_out, void* dlogits, void* stream);
 
+/* ---- K19 UnFuSeD self-distillation loss: src/upstream/unfused/upstream_expert.py:141-168, src/utils/utils.py:191-197
+ * (original extras/unfused/moco_model.py:286-342).  z1..z3 (students) and t (teacher): fp32 [B][ld] logits, ld >= C,
+ * ld % 4 == 0, columns [C, ld) never used (they may hold NaN); label int64 [B].
+ *   loss4 += {total, CE, KL, MSE}:  CE = alpha sum_h mean CE(z_h, y) + mean CE(t, y),
+ *                                   KL = beta sum_h batchmean KL(softmax(t) || softmax(z_h))  (target NOT detached),
+ *                                   MSE = gamma sum_h mean (2 - 2 cos(z_h, t))  (F.normalize eps 1e-12).
+ * dz1..dz3, dt: gradients in the same [B][ld] layout, fp32 (gdtype 0) or bf16 (gdtype 1), columns [C, ld) written as zeros;
+ * all four NULL = forward only, any mixture is EINVAL.  2 <= C <= 4096 (a row's four vectors live in one workgroup's
+ * registers).  A label outside [0, C) is never used as an index and adds NaN to all four loss slots.  One launch. */
+int audiossl_unfused_loss(int gdtype, const float* z1, const float* z2, const float* z3, const float* t,
+                          const long long* label, int B, int C, long ld, float alpha, float beta, float gamma,
+                          float* loss4, void* dz1, void* dz2, void* dz3, void* dt, void* stream);
+
 /* ---- row softmax: nn.Softmax(dim=1) closing SLICER's cluster projector (src/upstream/slicer/upstream_encoder.py:15-20);
  * fp32 [M][C]; bwd: gx = y * (gy - sum_c gy*y). */
 int audiossl_softmax_rows_fwd(const float* x, float* y, int M, int C, void* stream);
