@@ -1,0 +1,174 @@
+"""Embeddings out of a checkpoint - the head of the reference's offline labeler, `compute_features`
+(`extras/decar-v2/utils.py:75-112`) and the `main` of `extras/decar-v2/store_clusters.py:64-160`: load a checkpoint, run the
+encoder in `model.eval()` (running BatchNorm statistics, no dropout) under `no_grad` over a file list without augmentation,
+final short batch included, and collect [N, d] features in file order.
+
+What an embedding is:
+  AudioNTT2020Task6  backbone = mean over time of the [N, T', d] encoder output (what the reference's probe feeds its Linear,
+                                `src/downstream/downstream_encoder.py:38-44`);
+                     head     = the expert's `encoder_q` / `encoder` output: max + mean over time, and `fc` where the wrapper has one.
+  ASTModel           backbone = the mean over the patch tokens before `fc` (`ast_work.py:229`), base224 and mvit alike;
+                     head     = the `fc` output, i.e. the module's own forward.
+The token mean is `ctx.pooled` of the engines' forward: nothing an existing call returns changes.
+Windows: `random` is the reference's `extract_window` draw; `center` (default) takes the centre crop / centre zero-pad, so two
+runs agree.  Single GPU.
+"""
+import importlib
+
+import torch
+import torch.nn.functional as F
+
+from src.utils import extract_window
+
+WINDOWS = ("center", "random")
+LAYERS = ("backbone", "head")
+_BASES = ("AudioNTT2020Task6", "ASTModel")
+
+
+# ------------------------------------------------------------------------------------- windows
+def center_start(n_samples, unit_length):
+    """(start, left_pad) of the centre window: the crop's first sample for a long clip, the zeros in front of a short one."""
+    if n_samples >= unit_length:
+        return (n_samples - unit_length) // 2, 0
+    return 0, (unit_length - n_samples) // 2
+
+
+def take_window(wav, unit_length, window="center"):
+    """1-D tensor -> [unit_length] tensor.  `random`: `extract_window` (draws from python `random` iff the clip is longer)."""
+    if window == "random":
+        return extract_window(wav, duration=unit_length)
+    if window != "center":
+        raise ValueError(f"window must be one of {WINDOWS}")
+    start, left = center_start(len(wav), unit_length)
+    if len(wav) < unit_length:
+        wav = F.pad(wav, (left, unit_length - len(wav) - left))
+    return wav[start:start + unit_length]
+
+
+# ------------------------------------------------------------------------------------- the model side
+def _resolve(model):
+    """expert | encoder wrapper | base encoder -> (wrapper, base encoder)."""
+    if repr(model) in _BASES:
+        return model, model
+    wrapper = getattr(model, "encoder_q", None)
+    if wrapper is None:
+        wrapper = getattr(model, "encoder", None)
+        if wrapper is None:
+            raise TypeError(f"{type(model).__name__} has no encoder_q / encoder to take embeddings from")
+        if repr(wrapper) in _BASES and not hasattr(model, "hparams"):
+            wrapper = model                                   # `model` is itself a wrapper around a base encoder
+    base = wrapper if repr(wrapper) in _BASES else getattr(wrapper, "encoder", None)
+    if repr(base) not in _BASES:
+        raise NotImplementedError(f"no embedding rule for a {type(base).__name__} base encoder")
+    return wrapper, base
+
+
+class Embedder:
+    """`Embedder(expert_or_encoder, layer="backbone"|"head", precision=None)`; `embedder(x)` maps a front-end batch
+    [B, 1, F, T] to float32 [B, d].  precision: "fp32" / "bf16" for the conv encoder (None = the module's own)."""
+
+    def __init__(self, model, layer="backbone", precision=None, input_shape=None):
+        if layer not in LAYERS:
+            raise ValueError(f"layer must be one of {LAYERS}")
+        self.model, self.layer = model, layer
+        self.wrapper, self.base = _resolve(model)
+        self.kind = repr(self.base)
+        self.precision = precision
+        self.input_shape = input_shape
+        self._front = None
+
+    # ---- front ends (no augmentation, no masking, no mixing)
+    def front_end(self):
+        if self._front is None:
+            if self.kind == "AudioNTT2020Task6":
+                from src.dataset.downstream_dataset import DownstreamFrontEnd
+                self._front = DownstreamFrontEnd()
+            else:
+                from src.dataset.mast_dataset import AUDIOSET_MEAN, AUDIOSET_STD, MastFrontEnd
+                b = self.base
+                fdim, tdim = self.input_shape or ((b.f_dim - 1) * b.cfg["fstride"] + 16, (b.t_dim - 1) * b.cfg["tstride"] + 16)
+                fb = MastFrontEnd(dict(num_mel_bins=fdim, target_length=tdim, freqm=0, timem=0, mixup=0.0, mean=AUDIOSET_MEAN,
+                                       std=AUDIOSET_STD, skip_norm=False)).fbank
+                # the feature chain of `make_features` (run_mvit.py:107-125); called below the planner, so nothing is drawn
+                self._front = lambda waves: fb(waves.cuda().float(), None, tdim, mean=AUDIOSET_MEAN, std=AUDIOSET_STD, skip_norm=False)
+        return self._front
+
+    def _forward(self, x):
+        if self.kind == "ASTModel":
+            b = self.base
+            out, c = b.engine_forward(b.param_dict(), b.weight_shadow(), x.float().contiguous(), b.cfg, need_ctx=True)
+            return out if self.layer == "head" else c.pooled
+        if self.layer == "backbone":
+            from src.downstream.downstream_encoder import MeanTFn
+            h = self.base(x)
+            return MeanTFn.apply(h[-1] if isinstance(h, tuple) else h)
+        if self.wrapper is self.base:
+            from src.functional import MaxMeanFn
+            h = self.base(x)
+            return MaxMeanFn.apply(h[-1] if isinstance(h, tuple) else h)
+        y = self.wrapper(x)
+        return y[0] if isinstance(y, tuple) else y
+
+    @torch.no_grad()
+    def __call__(self, x):
+        mods = list(self.model.modules())
+        flags = [m.training for m in mods]
+        own = getattr(self.base, "precision", None)
+        self.model.eval()
+        if self.precision is not None and self.kind == "AudioNTT2020Task6":
+            from src import _native as N
+            self.base.precision = {"fp32": N.F32, "bf16": N.BF16}.get(self.precision, self.precision)
+        try:
+            return self._forward(x).float()
+        finally:
+            if own is not None:
+                self.base.precision = own
+            for m, f in zip(mods, flags):
+                m.training = f
+
+
+@torch.no_grad()
+def extract_embeddings(embedder, files, batch_size=64, window="center", duration=1.0, pcm=False):
+    """files: paths (WAV / .npy, any rate) -> float32 [N, d] on the device, in file order.  duration in seconds.
+    pcm: ship the windows in the files' own sample formats and convert on the GPU (conv encoders; `PcmBatch`)."""
+    from src.dataset.upstream_dataset import load_audio
+    if window not in WINDOWS:
+        raise ValueError(f"window must be one of {WINDOWS}")
+    unit = int(duration * 16000)
+    front = embedder.front_end()
+    pcm = bool(pcm) and embedder.kind == "AudioNTT2020Task6"
+    files = list(files)
+    out = []
+    for i in range(0, len(files), batch_size):
+        clips = [load_audio(f, 16000, raw=pcm) for f in files[i:i + batch_size]]
+        if pcm:
+            from src.dataset.ingest import PcmBatch
+            from src.utils.utils import window_start
+            wins = []
+            for c in clips:
+                start = window_start(len(c), unit)[0] if window == "random" else center_start(len(c), unit)[0]
+                wins.append(c.window(start, unit) if hasattr(c, "window") else c[start:start + unit])
+            batch = PcmBatch.pack(wins, [0] * len(wins), unit)
+        else:
+            batch = torch.stack([take_window(torch.from_numpy(c) if not torch.is_tensor(c) else c, unit, window) for c in clips])
+        n = len(clips)
+        if embedder.kind == "ASTModel" and n % 2:            # the transformer engines take batch * tokens in multiples of 8
+            batch = torch.cat([batch, batch[-1:]])
+        out.append(embedder(front(batch))[:n])
+    return torch.cat(out)
+
+
+def load_embedder(checkpoint, upstream, config=None, layer="backbone", precision=None):
+    """Checkpoint -> Embedder through `Upstream_Expert.load_from_checkpoint`, the way `load_pretrained_encoder` does it.
+    config: overrides the checkpoint's (a dict, as `train_upstream.load_config` returns)."""
+    try:
+        mod = importlib.import_module(f"src.upstream.{upstream}.upstream_expert")
+    except ModuleNotFoundError as e:
+        raise ValueError(f"src/upstream/{upstream} has no Upstream_Expert to load a checkpoint with") from e
+    over = {} if config is None else {"config": config}
+    expert = mod.Upstream_Expert.load_from_checkpoint(checkpoint, strict=False, **over).cuda()
+    shape = None
+    inp = expert.config["pretrain"]["input"]
+    if repr(_resolve(expert)[1]) == "ASTModel":
+        shape = (inp["n_mels"], 1 + int(inp["length_wave"] * inp["sampling_rate"]) // 160)
+    return Embedder(expert, layer=layer, precision=precision, input_shape=shape)

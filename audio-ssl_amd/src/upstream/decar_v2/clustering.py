@@ -93,10 +93,13 @@ class Kmeans(object):
         return loss
 
 
-def write_pseudolabel_csv(paths, kmeans, out_csv):
-    """`store_clusters.py:142-159`: one `path,pseudolabel` line per file, in file order."""
+def write_pseudolabel_csv(paths, kmeans, out_csv, header=None):
+    """`store_clusters.py:142-159`: one `path,pseudolabel` line per file, in file order.  header: a first line (the
+    `files,label` that `train_upstream.py --upstream unfused` reads); the reference writes none."""
     labels = rearrange_clusters(kmeans.images_lists)
     with open(out_csv, "w") as f:
+        if header:
+            f.write(header + "\n")
         for p, l in zip(paths, labels):
             f.write(f"{p},{int(l)}\n")
     return labels

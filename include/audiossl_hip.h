@@ -455,6 +455,24 @@ int audiossl_unfused_loss(int gdtype, const float* z1, const float* z2, const fl
                           const long long* label, int B, int C, long ld, float alpha, float beta, float gamma,
                           float* loss4, void* dz1, void* dz2, void* dz3, void* dt, void* stream);
 
+/* ---- K20 k-NN evaluation on frozen embeddings (csrc/knn.hip).  No counterpart runs in the reference: its `validation_step`s
+ * import `precision_at_k` and stop there; this is the weighted k-NN classifier of InstDisc / MoCo / DINO (`knn_classifier`,
+ * DINO eval_knn.py) and replaces `sim = q @ bank.T; sim.topk(k)` plus the one-hot scatter / exp(sim / T) vote after it.
+ * knn_topk: q [Nq][D], bank [Nb][D] row-major bf16 (the caller normalises: audiossl_l2norm_fwd writes such rows), fp32
+ *   accumulation on the MFMA pipe.  top_sim / top_idx [Nq][k]: each query's k largest dot products in descending order and
+ *   their bank rows, equal values by ascending row.  The [Nq][Nb] matrix is never stored; `workspace` (device,
+ *   audiossl_knn_workspace bytes, needs no clearing) holds the per-split partial lists when the bank is split over workgroups.
+ *   1 <= k <= 128, k <= Nb < 2^31, Nq >= 1, D % 32 == 0, 32 <= D <= 4096; inputs finite.
+ * knn_workspace (host): bytes for knn_topk, O(Nq k splits), non-decreasing in Nq and in k.
+ * knn_vote: neighbour j weighs exp((top_sim[j] - row max) * inv_t) (inv_t = 0: majority vote); pred = the int64 label
+ *   (bank_label[top_idx[j]], compared only, never an index) with the largest summed weight, ties to the smaller label; conf = that
+ *   sum / the row's total.  A row with a top_idx outside [0, Nb) reads no label and gets pred = -1, conf = NaN. */
+int audiossl_knn_workspace(int Nq, long Nb, int k, long* bytes);
+int audiossl_knn_topk(const void* q, const void* bank, int Nq, long Nb, int D, int k, float* top_sim, int* top_idx,
+                      void* workspace, long workspace_bytes, void* stream);
+int audiossl_knn_vote(const float* top_sim, const int* top_idx, const long long* bank_label, int Nq, int k, long Nb,
+                      float inv_t, long long* pred, float* conf, void* stream);
+
 /* ---- row softmax: nn.Softmax(dim=1) closing SLICER's cluster projector (src/upstream/slicer/upstream_encoder.py:15-20);
  * fp32 [M][C]; bwd: gx = y * (gy - sum_c gy*y). */
 int audiossl_softmax_rows_fwd(const float* x, float* y, int M, int C, void* stream);
