@@ -108,19 +108,14 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const TY* __restr
     o.store(P + idx * 8);
 }
 
-// The same with the BatchNorm finalisation folded in (train mode, 64 channels): every workgroup turns the fp64 column sums into
-// scale / shift itself (64 lanes, a few flops each) instead of waiting for a one-workgroup bn_finalize launch between the
-// convolution and the pooling - one graph node and one dependent-launch gap less per conv block; workgroup 0 also stores
-// scale / shift / mean / rstd for the backward and updates the running buffers.
-template <typename TY, typename T_>
-__global__ __launch_bounds__(256) void bn_relu_pool_train_fwd_kernel(const TY* __restrict__ Y, const double* __restrict__ sum,
-                                                                     const double* __restrict__ sumsq, int stat_rep, double count,
-                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                     float* running_mean, float* running_var, float momentum, float eps,
-                                                                     T_* __restrict__ P, float* __restrict__ scale,
-                                                                     float* __restrict__ shift, float* __restrict__ save_mean,
-                                                                     float* __restrict__ save_rstd, int N, int Ti, int Fi) {
-    __shared__ float sc_s[64], sh_s[64];
+// The finalisation the train-mode kernels below start with: the first 64 threads of every workgroup fold the replicated fp64 sums
+// into scale / shift (left in LDS, behind a barrier); workgroup 0 also stores scale / shift / mean / rstd for the backward and
+// updates the running buffers.  One function, so every kernel that uses it produces the same bits.
+__device__ __forceinline__ void bn_train_prologue(const double* __restrict__ sum, const double* __restrict__ sumsq, int stat_rep,
+                                                  double count, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  float* running_mean, float* running_var, float momentum, float eps,
+                                                  float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ save_mean,
+                                                  float* __restrict__ save_rstd, float* sc_s, float* sh_s) {
     if (threadIdx.x < 64) {
         const int c = threadIdx.x;
         const double g = (double)gamma[c], b = (double)beta[c];
@@ -142,6 +137,23 @@ __global__ __launch_bounds__(256) void bn_relu_pool_train_fwd_kernel(const TY* _
         }
     }
     __syncthreads();
+}
+
+// The same with the BatchNorm finalisation folded in (train mode, 64 channels): every workgroup turns the fp64 column sums into
+// scale / shift itself (64 lanes, a few flops each) instead of waiting for a one-workgroup bn_finalize launch between the
+// convolution and the pooling - one graph node and one dependent-launch gap less per conv block; workgroup 0 also stores
+// scale / shift / mean / rstd for the backward and updates the running buffers.
+template <typename TY, typename T_>
+__global__ __launch_bounds__(256) void bn_relu_pool_train_fwd_kernel(const TY* __restrict__ Y, const double* __restrict__ sum,
+                                                                     const double* __restrict__ sumsq, int stat_rep, double count,
+                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                     float* running_mean, float* running_var, float momentum, float eps,
+                                                                     T_* __restrict__ P, float* __restrict__ scale,
+                                                                     float* __restrict__ shift, float* __restrict__ save_mean,
+                                                                     float* __restrict__ save_rstd, int N, int Ti, int Fi) {
+    __shared__ float sc_s[64], sh_s[64];
+    bn_train_prologue(sum, sumsq, stat_rep, count, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, save_mean,
+                      save_rstd, sc_s, sh_s);
     const int To = Ti / 2, Fo = Fi / 2;
     const long total = (long)N * To * Fo * 8;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -166,6 +178,46 @@ __global__ __launch_bounds__(256) void bn_relu_pool_train_fwd_kernel(const TY* _
 #pragma unroll
     for (int i = 0; i < 8; ++i) o.set(i, m[i]);
     o.store(P + idx * 8);
+}
+
+// BatchNorm + ReLU on the POOLED raw map conv3x3_pool_fwd left: Praw [N][To][Fo][64] holds, per channel, the window's maximum of
+// the conv output (gamma >= 0) or its minimum (gamma < 0), and y -> max(0, scale * y + shift) is monotone with the sign of gamma,
+// so P = max(0, scale * Praw + shift) is what the kernels above compute from the whole of Y - from a quarter of the bytes.
+// Elementwise, the same thread reads and writes an element: P may be Praw.  vecs = 16-byte vectors; the stride is a multiple
+// of 8, so a thread keeps its channel chunk.
+template <typename T_>
+__device__ __forceinline__ void bn_relu_pooled_apply(const T_* Praw, const float* sc_s, const float* sh_s, T_* P, long vecs) {
+    const int c8 = threadIdx.x & 7;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { sc[i] = sc_s[c8 * 8 + i]; sh[i] = sh_s[c8 * 8 + i]; }
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < vecs; idx += (long)gridDim.x * 256) {
+        const Vec8<T_> v = Vec8<T_>::load(Praw + idx * 8);
+        Vec8<T_> o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o.set(i, fmaxf(0.f, sc[i] * v.get(i) + sh[i]));
+        o.store(P + idx * 8);
+    }
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void bn_relu_pooled_fwd_kernel(const T_* Praw, const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift, T_* P, long vecs) {
+    bn_relu_pooled_apply<T_>(Praw, scale, shift, P, vecs);
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void bn_relu_pooled_train_fwd_kernel(const T_* Praw, const double* __restrict__ sum,
+                                                                       const double* __restrict__ sumsq, int stat_rep, double count,
+                                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                       float* running_mean, float* running_var, float momentum,
+                                                                       float eps, T_* P, float* __restrict__ scale,
+                                                                       float* __restrict__ shift, float* __restrict__ save_mean,
+                                                                       float* __restrict__ save_rstd, long vecs) {
+    __shared__ float sc_s[64], sh_s[64];
+    bn_train_prologue(sum, sumsq, stat_rep, count, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, save_mean,
+                      save_rstd, sc_s, sh_s);
+    bn_relu_pooled_apply<T_>(Praw, sc_s, sh_s, P, vecs);
 }
 
 // xl[n][f*64+c] = mean_t P[n][t][f][c].  A workgroup owns one image and a strip of 64 vectors (512 features); its four
@@ -538,6 +590,37 @@ extern "C" int audiossl_bn_relu_pool_train_fwd(int dtype, int ydtype, const void
                            static_cast<const TY*>(Y), sum, sumsq, stat_replicas, count, gamma, beta, running_mean, running_var,
                            momentum, eps, static_cast<TO*>(P), scale, shift, save_mean, save_rstd, N, Ti, Fi);
     }, ydtype);
+    ASSL_LAUNCH_CHECK();
+}
+
+// Praw, P [N][To][Fo][64] of `dtype`; P may be Praw (in place).  `count` = elements per channel the sums ran over (N * Ti * Fi of
+// the UNPOOLED conv output).
+extern "C" int audiossl_bn_relu_pooled_fwd(int dtype, const void* Praw, const float* scale, const float* shift, void* P, int N,
+                                           int To, int Fo, void* stream) {
+    ASSL_REQUIRE(Praw && scale && shift && P && N > 0 && To > 0 && Fo > 0 && (dtype == 0 || dtype == 1));
+    const long vecs = (long)N * To * Fo * 8;
+    const int grid = (int)min((long)2048, (vecs + 255) / 256);            // 2,048 x 256 threads: a multiple of 8, see the kernel
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_relu_pooled_fwd_kernel<T>), dim3(grid), dim3(256), 0, S_(stream), static_cast<const T*>(Praw), scale, shift,
+                           static_cast<T*>(P), vecs);
+    });
+    ASSL_LAUNCH_CHECK();
+}
+
+extern "C" int audiossl_bn_relu_pooled_train_fwd(int dtype, const void* Praw, const double* sum, const double* sumsq, int stat_replicas,
+                                                 double count, const float* gamma, const float* beta, float* running_mean,
+                                                 float* running_var, float momentum, float eps, void* P, float* scale, float* shift,
+                                                 float* save_mean, float* save_rstd, int N, int To, int Fo, void* stream) {
+    ASSL_REQUIRE(Praw && sum && sumsq && gamma && beta && P && scale && shift && save_mean && save_rstd && count > 0.0);
+    ASSL_REQUIRE(stat_replicas >= 1 && (stat_replicas == 1 || sumsq == sum + 64));
+    ASSL_REQUIRE(N > 0 && To > 0 && Fo > 0 && (dtype == 0 || dtype == 1));
+    const long vecs = (long)N * To * Fo * 8;
+    const int grid = (int)min((long)2048, (vecs + 255) / 256);
+    assl_dispatch(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_relu_pooled_train_fwd_kernel<T>), dim3(grid), dim3(256), 0, S_(stream), static_cast<const T*>(Praw), sum,
+                           sumsq, stat_replicas, count, gamma, beta, running_mean, running_var, momentum, eps, static_cast<T*>(P), scale,
+                           shift, save_mean, save_rstd, vecs);
+    });
     ASSL_LAUNCH_CHECK();
 }
 

@@ -32,6 +32,7 @@ typedef __attribute__((address_space(3))) bf16x4* lds4_t;
 struct ConvArgs {
     const bf16* X; const bf16* W; const float* bias; bf16* Y; double* sum; double* sumsq;
     int Ti, rows_total, tiles, out_f32, dbg, stat_rep;
+    const float* gamma; bf16* Praw;                               // pooled emission (conv3x3_ws_kernel<..., POOL>) only
 };
 
 template <int FI, int PITCH, int NTH = 256>
@@ -220,6 +221,23 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_kernel(ConvArgs a) {
 // separate write requests per instruction, which made the stores the second largest cost of the kernel above (37 us at
 // B = 512).  Each wave transposes its 32-pixel row-tiles through a private, swizzled LDS staging area instead and writes whole
 // pixels: 1 KB contiguous per store instruction.
+// POOL (bf16 output with STATS, Ti even): the wave also forms the 2x2 max-pool windows of the conv output from its staging area and
+// stores them to Praw [N][Ti/2][FI/2][64].  BatchNorm and ReLU are monotone per channel - increasing for gamma >= 0, decreasing
+// for gamma < 0 - so max(0, scale * y + shift) over a window equals that expression at the window's raw maximum (gamma >= 0) or
+// minimum (gamma < 0): the BN + ReLU pass then runs over a quarter of the pixels (bn_relu_pooled_*_fwd).  A wave's two staging
+// tiles are rows g, g + 1 (FI = 32) or two row pairs (FI = 16) with g even, and g = n * Ti + t keeps the parity of t when Ti is
+// even: every window sits inside one wave's staging, and the wave's pooled pixels are contiguous in Praw (pooled row g / 2).
+// KEEP_Y = false drops the store of Y (nothing reads it when the pass has no backward); the statistics do not change.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// v_max_f32 / v_max3_f32 without the canonicalising self-max that fmaxf gets for operands of unknown origin
+__device__ __forceinline__ float vmax4(float a, float b, float c, float d) {
+    float t, r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(t) : "v"(a), "v"(b), "v"(c));
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(t), "v"(d));
+    return r;
+}
+
 template <int FI>
 struct WsGeom {
     static constexpr int TT = 256 / FI, COLS = FI + 2, ROWS = TT + 2, SEGS = FI / 8;
@@ -228,10 +246,13 @@ struct WsGeom {
     static constexpr int BYTES = ROWS * COLS * 128;
 };
 
-template <int FI, bool STATS, bool F32OUT, int PF = 2>
+template <int FI, bool STATS, bool F32OUT, int PF = 2, bool POOL = false, bool KEEP_Y = true>
 __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
+    static_assert(!POOL || (STATS && !F32OUT), "pooled emission: bf16 output with statistics");
+    static_assert(KEEP_Y || POOL, "a convolution that stores nothing");
     using G = WsGeom<FI>;
     constexpr int TT = G::TT, COLS = G::COLS;
+    const int dbg = POOL ? 0 : a.dbg;                                           // the pooled forms have no ablation modes (and no SGPR to hold the flags)
     typedef __attribute__((address_space(3))) void* lptr_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* const biasl = reinterpret_cast<float*>(smem + 2 * G::BYTES);          // [64]
@@ -240,10 +261,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
     char* const stg = reinterpret_cast<char*>(red + 4 * 64 * 2) + (threadIdx.x >> 6) * 64 * OPIX;   // this wave's 2 x 32-pixel staging tiles
     char* const zblk = reinterpret_cast<char*>(red + 4 * 64 * 2) + 4 * 64 * OPIX;                   // 512 bytes of zeros
     if (threadIdx.x < 32) *reinterpret_cast<f32x4*>(zblk + threadIdx.x * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
+    // POOL: sign-bit masks of the channels with gamma < 0, [2][8 chunks][4 dwords]: set 0 in channel order, set 1 with the two
+    // 8-byte halves of a chunk swapped (the order odd staging keys store them in)
+    unsigned* const gsign = reinterpret_cast<unsigned*>(zblk + 512);
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 31, h = lane >> 5;
-    long* const rts = (!STATS && (a.dbg & 16) && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))
+    long* const rts = (!STATS && (dbg & 16) && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))
                           ? reinterpret_cast<long*>(a.sum) + 64 + (blockIdx.x ? 8 : 0) : nullptr;
     if (rts) rts[0] = __builtin_amdgcn_s_memrealtime();
 
@@ -284,6 +308,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
         *reinterpret_cast<f32x4*>(smem + b * G::BYTES + (r * COLS + side * (FI + 1)) * 128 + c8 * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (threadIdx.x < 64) biasl[threadIdx.x] = a.bias ? a.bias[threadIdx.x] : 0.f;
+    if (POOL && threadIdx.x >= 64 && threadIdx.x < 128) {
+        const int t = threadIdx.x - 64, c = (t >> 2) & 7, j = (t >> 5) ? ((t & 3) ^ 2) : (t & 3);
+        const float ga = a.gamma[c * 8 + 2 * j], gb = a.gamma[c * 8 + 2 * j + 1];
+        gsign[t] = (ga < 0.f ? 0x8000u : 0u) | (gb < 0.f ? 0x80000000u : 0u);
+    }
 
     if (rts) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); rts[3] = __builtin_amdgcn_s_memrealtime(); }
     // DMA addressing: lane -> (pixel of the 8-pixel segment, chunk position); source chunk = position ^ (halo column & 7)
@@ -333,14 +362,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
-    long* const ts = (!STATS && (a.dbg & 16) && blockIdx.x == 0 && threadIdx.x == 0) ? reinterpret_cast<long*>(a.sum) : nullptr;
+    long* const ts = (!STATS && (dbg & 16) && blockIdx.x == 0 && threadIdx.x == 0) ? reinterpret_cast<long*>(a.sum) : nullptr;
     int tsi = 0;
     if (rts) rts[1] = __builtin_amdgcn_s_memrealtime();
     for (; tile < a.tiles; tile += gridDim.x, cur ^= 1) {
         if (ts) ts[tsi++] = __builtin_amdgcn_s_memtime();
         const int g0 = tile * TT;
         const int next = tile + gridDim.x;
-        if (next < a.tiles && !(a.dbg & 2)) dma_tile(next * TT, smem + (cur ^ 1) * G::BYTES);
+        if (next < a.tiles && !(dbg & 2)) dma_tile(next * TT, smem + (cur ^ 1) * G::BYTES);
         const char* const hl = smem + cur * G::BYTES;
 
         // rows above / below the image (the global row enumeration runs across images) must read as zeros: such a
@@ -376,7 +405,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
             for (int i = 0; i < 2; ++i)
                 f[i] = Vec8<bf16>::load(reinterpret_cast<const bf16*>((const char*)(lptr_t)(size_t)(bdt[i][dt] + df * 128 + (hs[df] ^ (cc * 32)))));
         };
-        if (!(a.dbg & 4)) {
+        if (!(dbg & 4)) {
 #pragma unroll
         for (int ks = 0; ks < PF; ++ks) fetch(ks, fa[ks]);
 #pragma unroll
@@ -398,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (ts) ts[tsi++] = __builtin_amdgcn_s_memtime();
         // epilogue: this lane's pixel, channels j * 32 + 8 * q + 4 * h + (0..3) in accumulator registers 4q..4q+3 -> staging
-        if (!(a.dbg & 1)) {
+        if (!(dbg & 1)) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 char* const st = stg + i * 32 * OPIX;
@@ -441,7 +470,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
                         f32x4 v = *reinterpret_cast<const f32x4*>(st + p * 128 + ((c ^ (k >> 1)) << 4));
                         if (k & 1) v = f32x4{v[2], v[3], v[0], v[1]};                  // the two 8-byte slots of the chunk sit swapped
                         if ((p >> (FI == 32 ? 5 : 4)) < prow_ok) {
-                            *reinterpret_cast<f32x4*>(yrow + p * 128 + c * 16) = v;
+                            if (KEEP_Y) *reinterpret_cast<f32x4*>(yrow + p * 128 + c * 16) = v;
                             if (STATS) {
                                 const bf16x8 hv = __builtin_bit_cast(bf16x8, v);
 #pragma unroll
@@ -452,6 +481,44 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(ConvArgs a) {
                             }
                         }
                     }
+                }
+            }
+            if (POOL) {
+                // lane -> (pooled pixel po of the store, 16-byte chunk cp); the window's four pixels share the staging key's
+                // parity (po & 1 = pl & 1), so the extremum is taken in stored order and the halves are swapped once.  Channels
+                // with gamma < 0 get their sign flipped before and after: min(x) = -max(-x).  The high bf16 of a dword is
+                // compared as it stands (the low half below it cannot change which high half wins), the low one shifted up.
+                const u32x4 sm = *reinterpret_cast<const u32x4*>(gsign + ((pl & 1) * 8 + cp) * 4);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int po = FI == 32 ? s * 8 + pl : pl;
+                    const int grow = g0 + (FI == 32 ? 2 * wave : 2 * (2 * wave + s));      // even: the window's first row
+                    const int pos = (cp ^ (po >> 1)) << 4;
+                    const char* const s0 = stg + (FI == 32 ? 0 : s * 32 * 128) + (2 * po) * 128;
+                    u32x4 q[4];
+                    q[0] = *reinterpret_cast<const u32x4*>(s0 + pos);
+                    q[1] = *reinterpret_cast<const u32x4*>(s0 + 128 + pos);
+                    if (FI == 32) {                                                        // second row = the second staging tile
+                        q[2] = *reinterpret_cast<const u32x4*>(s0 + 32 * 128 + pos);
+                        q[3] = *reinterpret_cast<const u32x4*>(s0 + 33 * 128 + pos);
+                    } else {                                                               // second row = pixels 16..31: key + 8
+                        q[2] = *reinterpret_cast<const u32x4*>(s0 + 16 * 128 + (pos ^ 64));
+                        q[3] = *reinterpret_cast<const u32x4*>(s0 + 17 * 128 + (pos ^ 64));
+                    }
+                    u32x4 r;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned d0 = q[0][j] ^ sm[j], d1 = q[1][j] ^ sm[j], d2 = q[2][j] ^ sm[j], d3 = q[3][j] ^ sm[j];
+                        const float hi = vmax4(__builtin_bit_cast(float, d0), __builtin_bit_cast(float, d1),
+                                               __builtin_bit_cast(float, d2), __builtin_bit_cast(float, d3));
+                        const float lo = vmax4(__builtin_bit_cast(float, d0 << 16), __builtin_bit_cast(float, d1 << 16),
+                                               __builtin_bit_cast(float, d2 << 16), __builtin_bit_cast(float, d3 << 16));
+                        r[j] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo), 0x07060302u) ^ sm[j];
+                    }
+                    const unsigned odd = 0u - (unsigned)(pl & 1);                          // a bit-select, not a lane mask held in SGPRs
+                    r = u32x4{(r[2] & odd) | (r[0] & ~odd), (r[3] & odd) | (r[1] & ~odd), (r[0] & odd) | (r[2] & ~odd), (r[1] & odd) | (r[3] & ~odd)};
+                    if (a.rows_total - grow >= 2)                                          // both rows of the window exist
+                        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(a.Praw) + ((grow >> 1) * (FI / 2) * 128 + po * 128 + cp * 16)) = r;   // < 2^31: a quarter of X
                 }
             }
         }
@@ -725,6 +792,39 @@ extern "C" int audiossl_conv3x3_fwd(const void* X, const void* W, const float* b
     if (Fi == 32) { if (nw == 8) CONV_LAUNCH(32, 8, 0); else CONV_LAUNCH(32, 4, 1); }
     else          { if (nw == 8) CONV_LAUNCH(16, 8, 2); else CONV_LAUNCH(16, 4, 3); }
 #undef CONV_LAUNCH
+    ASSL_LAUNCH_CHECK();
+}
+
+// The forward convolution with the 2x2 max-pool taken in its epilogue (see conv3x3_ws_kernel, POOL).  Praw [N][Ti/2][Fi/2][64]
+// bf16 gets, per channel, the window's maximum of the stored conv output where gamma >= 0 and its minimum where gamma < 0;
+// Y may be NULL (not stored).  The statistics are those of audiossl_conv3x3_fwd, bit for bit.  Ti even, Fi 32 or 16.
+extern "C" int audiossl_conv3x3_pool_fwd(const void* X, const void* W, const float* bias, const float* gamma, void* Y, void* Praw,
+                                         double* sum, double* sumsq, int stat_replicas, int N, int Ti, int Fi, void* stream) {
+    ASSL_REQUIRE(X && W && gamma && Praw && sum && sumsq && N > 0 && Ti > 0 && (Ti % 2) == 0 && (Fi == 32 || Fi == 16));
+    ASSL_REQUIRE(stat_replicas >= 1 && stat_replicas <= 64 && (stat_replicas == 1 || sumsq == sum + 64));
+    const int rows = N * Ti, TT = 256 / Fi, tiles = (rows + TT - 1) / TT;
+    ASSL_REQUIRE((long)rows * Fi * 128 < 0x7FFFFF00L);            // the halo DMA addresses X through a 32-bit buffer offset
+    if (!ASSL_ALIGNED16(X) || !ASSL_ALIGNED16(W) || !ASSL_ALIGNED16(Y) || !ASSL_ALIGNED16(Praw)) return ASSL_EALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (sumsq == sum + 64) {
+        ASSL_ZERO(sum, sizeof(double) * 128 * stat_replicas, s);
+    } else {
+        ASSL_ZERO(sum, sizeof(double) * 64, s);
+        ASSL_ZERO(sumsq, sizeof(double) * 64, s);
+    }
+    ConvArgs a{static_cast<const bf16*>(X), static_cast<const bf16*>(W), bias, static_cast<bf16*>(Y), sum, sumsq, Ti, rows, tiles, 0, 0,
+               stat_replicas, gamma, static_cast<bf16*>(Praw)};
+    const int grid = tiles < 256 ? tiles : 256;
+    static bool pattr[4] = {false, false, false, false};
+#define POOL_LAUNCH(FI_, KEEP_, SLOT)                                                                     \
+    do {                                                                                                  \
+        const size_t lds = 2 * WsGeom<FI_>::BYTES + sizeof(float) * (64 + 4 * 64 * 2) + 4 * 64 * 128 + 512 + 256; \
+        if (!pattr[SLOT]) { if (set_lds(conv3x3_ws_kernel<FI_, true, false, 2, true, KEEP_>, lds)) return ASSL_ELAUNCH; pattr[SLOT] = true; } \
+        hipLaunchKernelGGL((conv3x3_ws_kernel<FI_, true, false, 2, true, KEEP_>), dim3(grid), dim3(256), lds, s, a); \
+    } while (0)
+    if (Fi == 32) { if (Y) POOL_LAUNCH(32, true, 0); else POOL_LAUNCH(32, false, 1); }
+    else          { if (Y) POOL_LAUNCH(16, true, 2); else POOL_LAUNCH(16, false, 3); }
+#undef POOL_LAUNCH
     ASSL_LAUNCH_CHECK();
 }
 

@@ -156,7 +156,7 @@ class AudioNTT2020Task6(nn.Module, NetworkCommonMixIn):
             x1, x2, x3, h = _EncoderFn.apply(self, x, keep, *params)
         else:
             x1, x2, x3, h, _ = E.encoder_forward(self.param_dict(), x, self.precision, keep=keep, p_drop=self.fc[2].p,
-                                                 train=self.training)
+                                                 train=self.training, need_bwd=False)
         if self.return_all_layers:
             return x1, x2, x3, h
         return h

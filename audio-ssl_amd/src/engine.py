@@ -341,11 +341,16 @@ STAT_REPLICAS = 8
 LOSS_REPLICAS = 32          # replicas of a Barlow loss term accumulated by the correlation GEMM's epilogue (gemm_multi_barlow)
 _BN_STATS_P = os.environ.get("AUDIOSSL_BN_STATS_P", "1") != "0"  # 0: BatchNorm-backward sums from a first sweep over the conv output
 _DP1_BF16 = os.environ.get("AUDIOSSL_DP1_BF16", "1") != "0"      # 0: the gradient into the stem backward stays fp32
+_CONV_POOL = os.environ.get("AUDIOSSL_CONV_POOL", "1") != "0"    # 0: the convolution stores only Y, BN + ReLU + pool read all of it
+_CONV_WS = int(os.environ.get("AUDIOSSL_CONV_WS", "1")) != 0     # the library's switch: the pooled emission exists in the default kernel only
 
 
-def _conv_block_fwd(dtype, Pin, Nimg, Ti, Fi, W, bias, bn, train, update_running, col, packed=None):
+def _conv_block_fwd(dtype, Pin, Nimg, Ti, Fi, W, bias, bn, train, update_running, col, packed=None, keep_y=True):
     """3x3 conv -> BN -> ReLU -> pool.  bf16: implicit-GEMM kernel with the batch statistics fused into its epilogue;
-    fp32 (validation path): im2col + exact-f32 MFMA GEMM + colstats.  Returns (Y, Pout, stats, Wf, Wd)."""
+    fp32 (validation path): im2col + exact-f32 MFMA GEMM + colstats.  Returns (Y, Pout, stats, Wf, Wd).
+    bf16 with an even Ti: the convolution also takes the 2x2 window extrema (max where gamma >= 0, min where gamma < 0: BN + ReLU
+    is monotone with the sign of gamma) and BN + ReLU run over the pooled map, in place; keep_y=False (no backward will read the
+    conv output) then stores no Y at all and returns None for it."""
     td = N.torch_dtype(dtype)
     if packed is not None:
         Wf, Wd = packed
@@ -354,9 +359,32 @@ def _conv_block_fwd(dtype, Pin, Nimg, Ti, Fi, W, bias, bn, train, update_running
         N.call("pack_conv_w", dtype, W, Wf, Wd)
     M = Nimg * Ti * Fi
     ad = _ad(dtype)
-    Y = _empty((M, 64), N.torch_dtype(ad), like=Pin)          # BatchNorm input: fp32 on the fp32 and bf16_hp paths
     gamma, beta, rm, rv = bn
     fused = dtype == N.BF16 and Fi in (16, 32)
+    if fused and ad == dtype and _CONV_POOL and _CONV_WS and Ti % 2 == 0 and M * 128 < 0x7FFFFF00:
+        rep = STAT_REPLICAS if (train and SYNC_BN is None) else 1
+        sq = ARENA.scratch((rep, 2, 64), torch.float64, Pin)          # the pooled kernel always takes the sums (eval mode ignores them)
+        Y = _empty((M, 64), td, like=Pin) if keep_y else None
+        Pout = _empty((Nimg, Ti // 2, Fi // 2, 64), td, like=Pin)
+        N.call("conv3x3_pool_fwd", Pin, Wf, bias, gamma, Y, Pout, sq[0, 0], sq[0, 1], rep, Nimg, Ti, Fi)
+        if train and SYNC_BN is None:
+            st = _empty((4, 64), torch.float32, like=Pin)
+            N.call("bn_relu_pooled_train_fwd", dtype, Pout, sq[0, 0], sq[0, 1], rep, float(M), gamma, beta, rm if update_running else None,
+                   rv if update_running else None, BN_MOMENTUM, BN_EPS, Pout, st[0], st[1], st[2], st[3], Nimg, Ti // 2, Fi // 2)
+            return Y, Pout, (st[0], st[1], st[2], st[3]), Wf, Wd
+        if train:
+            st = _empty((4, 64), torch.float32, like=Pin)
+            sq = sq[0]
+            SYNC_BN.all_reduce(sq)
+            N.call("bn_finalize", sq[0], sq[1], 1, float(M * SYNC_BN.world), 64, gamma, beta, rm if update_running else None,
+                   rv if update_running else None, BN_MOMENTUM, BN_EPS, st[0], st[1], st[2], st[3])
+            scale, shift, mean, rstd = st[0], st[1], st[2], st[3]
+        else:
+            scale, shift = _bn_eval(Pin, 64, gamma, beta, rm, rv)
+            mean = rstd = None
+        N.call("bn_relu_pooled_fwd", dtype, Pout, scale, shift, Pout, Nimg, Ti // 2, Fi // 2)
+        return Y, Pout, (scale, shift, mean, rstd), Wf, Wd
+    Y = _empty((M, 64), N.torch_dtype(ad), like=Pin)          # BatchNorm input: fp32 on the fp32 and bf16_hp paths
     # batch statistics: 8 replicas of the (sum | sum of squares) accumulator when the pooling launch folds them itself
     # (256 workgroups adding into one set of 128 addresses cost ~12 us at the end of the convolution)
     rep = STAT_REPLICAS if (fused and train and SYNC_BN is None) else 1
@@ -418,13 +446,15 @@ def stem_moments_pair(xa, xb=None):
 
 
 def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_running=True, want_layers=True, Wc=None,
-                    layer_out=None, before_fc=None, stem_moments=None):
+                    layer_out=None, before_fc=None, stem_moments=None, need_bwd=True):
     """P: dict of fp32 device tensors with the reference's state_dict keys (features_1.0.weight, ...).
     x [N,1,F,T] fp32.  keep: uint8 [N*T3, d] dropout keep-mask or None (no dropout).
     Wc: optional {"fc.0.weight", "fc.3.weight"} already in the activation dtype (flat shadow); layer_out: optional
     (x1, x2, x3) output buffers [N, F*64] (e.g. halves of the stacked projector inputs).
     stem_moments: this view's row of `stem_moments_pair` when the caller has already taken the stem's tap moments (both views of a
     step in one launch); only where `stem_fused(dtype, train)` holds.
+    need_bwd=False: no encoder_backward will follow this call (key / target encoders, no-grad and evaluation passes) - the conv
+    blocks then need not store their unpooled outputs (ctx.Y2 / ctx.Y3 are None where they did not).
     Returns (x1, x2, x3, H2 [N,T3,d]) in the activation dtype and the ctx for the backward."""
     Nimg, _, F, T = x.shape
     assert F == 64, "the HIP encoder is built for n_mels = 64 (the reference's only setting)"
@@ -432,6 +462,7 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     c = EncoderCtx()
     c.P = P
     c.dtype, c.N, c.F, c.T, c.train, c.p_drop = dtype, Nimg, F, T, train, p_drop
+    c.need_bwd = need_bwd
     img = x.reshape(Nimg, F, T).contiguous()
     c.img = img
     w1 = P["features_1.0.weight"].reshape(64, 9)
@@ -478,11 +509,13 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     packs = [_empty((64, 576), td, like=x) for _ in range(4)]         # both layers' (forward, data-gradient) layouts: one launch
     N.call("pack_conv_w2", dtype, P["features_2.0.weight"], packs[0], packs[1], P["features_3.0.weight"], packs[2], packs[3])
     c.Y2, c.P2, c.st2, c.W2f, c.W2d = _conv_block_fwd(dtype, c.P1, Nimg, T1, F1, P["features_2.0.weight"],
-                                                       P["features_2.0.bias"], bn2, train, update_running, col, packed=packs[:2])
+                                                       P["features_2.0.bias"], bn2, train, update_running, col, packed=packs[:2],
+                                                       keep_y=need_bwd)
     T2, F2 = T1 // 2, F1 // 2
     bn3 = (P["features_3.1.weight"], P["features_3.1.bias"], P["features_3.1.running_mean"], P["features_3.1.running_var"])
     c.Y3, c.P3, c.st3, c.W3f, c.W3d = _conv_block_fwd(dtype, c.P2, Nimg, T2, F2, P["features_3.0.weight"],
-                                                       P["features_3.0.bias"], bn3, train, update_running, col, packed=packs[2:])
+                                                       P["features_3.0.bias"], bn3, train, update_running, col, packed=packs[2:],
+                                                       keep_y=need_bwd)
     del col
     T3, F3 = T2 // 2, F2 // 2
     c.dims = (T1, F1, T2, F2, T3, F3)
@@ -573,6 +606,7 @@ def encoder_backward(c, G, dA2=None, dH2=None, dx1=None, dx2=None, dx3=None, dx_
     T1, F1, T2, F2, T3, F3 = c.dims
     td = N.torch_dtype(dtype)
     assert c.train, "backward needs a train-mode forward (batch statistics)"
+    assert c.need_bwd, "this forward ran with need_bwd=False: the conv outputs were not kept"
     if dA2 is None:
         dA2 = _empty((M, d), td, like=c.H2)
         N.call("relu_bwd", dtype, dH2.contiguous(), c.H2, dA2, M * d)

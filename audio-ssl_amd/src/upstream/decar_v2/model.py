@@ -85,7 +85,8 @@ class AudioNTT2020(nn.Module):
         params = self.encoder_parameters()
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return _EncoderFn.apply(self, x, keep, *params)[3]
-        return E.encoder_forward(self.param_dict(), x, self.precision, keep=keep, p_drop=self.fc[2].p, train=self.training)[3]
+        return E.encoder_forward(self.param_dict(), x, self.precision, keep=keep, p_drop=self.fc[2].p, train=self.training,
+                                 need_bwd=False)[3]
 
     def project(self, z):
         ph = self.projection_head

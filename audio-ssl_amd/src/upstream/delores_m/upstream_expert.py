@@ -126,7 +126,7 @@ class Upstream_Expert(MocoQueueMixin, FusedExpertMixin, UpstreamModule):
             keepk = ek.encoder.next_keep_mask(B, x.shape[-1])
             _, _, _, Hk, _ = E.encoder_forward(ek.encoder.param_dict(), x, dt, keep=keepk, p_drop=0.3, train=self.training,
                                                Wc=strip(Wk, "encoder."), layer_out=tuple(y[B:] for y in Ys),
-                                               stem_moments=None if moms is None else moms[1])
+                                               stem_moments=None if moms is None else moms[1], need_bwd=False)
             yk, _ = E.maxmean_forward(dt, Hk)
             wk = Wk["fc.weight"]
             return E.linear_fwd(dt, yk, wk, B, wk.shape[0], wk.shape[1], bias=ek.fc.bias.data, out_f32=1)

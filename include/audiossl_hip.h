@@ -190,6 +190,16 @@ int audiossl_bn_relu_pool_train_fwd(int dtype, int ydtype, const void* Y, const 
                                     double count, const float* gamma, const float* beta, float* running_mean, float* running_var,
                                     float momentum, float eps, void* P, float* scale, float* shift, float* save_mean, float* save_rstd,
                                     int N, int Ti, int Fi, void* stream);
+/* BatchNorm + ReLU of a conv block (`audiontt.py:52-60`) on the POOLED raw map that conv3x3_pool_fwd leaves: Praw [N][To][Fo][64]
+ * holds per channel the 2x2 window's maximum of the conv output (gamma >= 0) or its minimum (gamma < 0); BN + ReLU is monotone with
+ * the sign of gamma, so P = max(0, scale * Praw + shift) equals bn_relu_pool_fwd of the whole conv output.  P may be Praw.
+ * bn_relu_pooled_train_fwd starts with the finalisation of bn_relu_pool_train_fwd (same bits); count = N * Ti * Fi of the conv output. */
+int audiossl_bn_relu_pooled_fwd(int dtype, const void* Praw, const float* scale, const float* shift, void* P, int N, int To, int Fo,
+                                void* stream);
+int audiossl_bn_relu_pooled_train_fwd(int dtype, const void* Praw, const double* sum, const double* sumsq, int stat_replicas,
+                                      double count, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                      float momentum, float eps, void* P, float* scale, float* shift, float* save_mean,
+                                      float* save_rstd, int N, int To, int Fo, void* stream);
 int audiossl_tmean_fwd(int dtype, int out_f32, const void* P, void* xl, int N, int To, int Fo, void* stream);
 /* x_1, x_2, x_3 of one encoder pass (`audiontt.py:76-93`) in one launch; with P1 == NULL and x1_parts given (out_f32 only)
  * x_1 = sum of the AUDIOSSL_CONV1_XL_PARTS parts conv1_fwd left */
@@ -252,6 +262,12 @@ int audiossl_unpack_conv_dw(const float* dWp, float* dW, void* stream);
  *   folded by a second kernel; null = every workgroup adds its result to dWp with fp32 atomics. */
 int audiossl_conv3x3_fwd(const void* X, const void* W, const float* bias, void* Y, int out_f32, double* sum,
                          double* sumsq, int stat_replicas, int N, int Ti, int Fi, void* stream);
+/* conv3x3_fwd with the 2x2 max-pool of the following BatchNorm -> ReLU -> MaxPool2d (`audiontt.py:52-60`) taken in its epilogue:
+ * Praw [N][Ti/2][Fi/2][64] bf16 = per channel the window's maximum of the stored conv output where gamma[c] >= 0, its minimum where
+ * gamma[c] < 0 (bn_relu_pooled_*_fwd turn it into the block's output).  Y bf16 may be NULL: the conv output is then not stored
+ * (a forward without a backward).  sum / sumsq as in conv3x3_fwd and required, bit for bit the same values.  Ti must be even. */
+int audiossl_conv3x3_pool_fwd(const void* X, const void* W, const float* bias, const float* gamma, void* Y, void* Praw, double* sum,
+                              double* sumsq, int stat_replicas, int N, int Ti, int Fi, void* stream);
 int audiossl_conv3x3_wgrad(const void* dY, const void* X, float* dWp, float* workspace, long workspace_floats, int N, int Ti,
                            int Fi, void* stream);
 

@@ -15,6 +15,16 @@ for Nimg, Ti, Fi in ((512, 50, 32), (512, 25, 16)):
     sq = torch.zeros(2, 64, dtype=torch.float64, device="cuda"); dWp = torch.zeros(64, 576, device="cuda")
     gf = 2.0 * Nimg * Ti * Fi * 64 * 576 / 1e6
     t = timeit(lambda: N.call("conv3x3_fwd", x, Wf, b, Y, 0, sq[0], sq[1], 1, Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} fwd+stats {t:7.1f} us {gf/t:6.1f} TF/s")
+    if Ti % 2 == 0:      # pooled emission (with / without the store of Y), then BN + ReLU on the pooled map against the pass over all of Y
+        gam = torch.rand(64, device="cuda") + 0.5; bet = torch.randn(64, device="cuda"); st = torch.empty(4, 64, device="cuda")
+        sq8 = torch.zeros(8, 2, 64, dtype=torch.float64, device="cuda"); Pr = torch.empty(Nimg, Ti // 2, Fi // 2, 64, device="cuda", dtype=torch.bfloat16)
+        t = timeit(lambda: N.call("conv3x3_fwd", x, Wf, b, Y, 0, sq8[0, 0], sq8[0, 1], 8, Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} fwd+stats (8 replicas) {t:7.1f} us {gf/t:6.1f} TF/s")
+        t = timeit(lambda: N.call("conv3x3_pool_fwd", x, Wf, b, gam, Y, Pr, sq8[0, 0], sq8[0, 1], 8, Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} fwd+stats+pool, Y kept {t:7.1f} us {gf/t:6.1f} TF/s")
+        t = timeit(lambda: N.call("conv3x3_pool_fwd", x, Wf, b, gam, None, Pr, sq8[0, 0], sq8[0, 1], 8, Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} fwd+stats+pool, no Y {t:7.1f} us {gf/t:6.1f} TF/s")
+        Po = torch.empty_like(Pr); cnt = float(Nimg * Ti * Fi)
+        t = timeit(lambda: N.call("bn_relu_pool_train_fwd", 1, 1, Y, sq8[0, 0], sq8[0, 1], 8, cnt, gam, bet, None, None, 0.1, 1e-5, Po, st[0], st[1], st[2], st[3], Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} bn_relu_pool_train_fwd (all of Y) {t:7.1f} us")
+        t = timeit(lambda: N.call("bn_relu_pooled_train_fwd", 1, Pr, sq8[0, 0], sq8[0, 1], 8, cnt, gam, bet, None, None, 0.1, 1e-5, Po, st[0], st[1], st[2], st[3], Nimg, Ti // 2, Fi // 2)); print(f"{(Nimg,Ti,Fi)} bn_relu_pooled_train_fwd {t:7.1f} us")
+        t = timeit(lambda: N.call("bn_relu_pooled_fwd", 1, Pr, st[0], st[1], Po, Nimg, Ti // 2, Fi // 2)); print(f"{(Nimg,Ti,Fi)} bn_relu_pooled_fwd {t:7.1f} us")
     t = timeit(lambda: N.call("conv3x3_fwd", dy, Wd, None, dx, 1, None, None, 1, Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} dgrad f32 {t:7.1f} us {gf/t:6.1f} TF/s")
     t = timeit(lambda: N.call("conv3x3_wgrad", dy, x, dWp, ws, ws.numel(), Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} wgrad 2-stage {t:7.1f} us {gf/t:6.1f} TF/s")
     t = timeit(lambda: N.call("conv3x3_wgrad", dy, x, dWp, None, 0, Nimg, Ti, Fi)); print(f"{(Nimg,Ti,Fi)} wgrad atomics {t:7.1f} us {gf/t:6.1f} TF/s")
