@@ -1,3 +1,4 @@
-"""What a user does with a checkpoint: embeddings (`embed`), k-NN evaluation (`knn`)."""
+"""What a user does with a checkpoint: embeddings (`embed`), k-NN evaluation (`knn`), layer similarity (`cka`)."""
+from src.evaluation.cka import cka_matrix, hsic_terms, kernel_cka, linear_cka, median_sigma2  # noqa: F401
 from src.evaluation.embed import Embedder, center_start, extract_embeddings, load_embedder, take_window  # noqa: F401
 from src.evaluation.knn import KnnClassifier, knn_predict, knn_topk, knn_topk_bf16, normalize_bf16  # noqa: F401

@@ -6,7 +6,10 @@ final short batch included, and collect [N, d] features in file order.
 What an embedding is:
   AudioNTT2020Task6  backbone = mean over time of the [N, T', d] encoder output (what the reference's probe feeds its Linear,
                                 `src/downstream/downstream_encoder.py:38-44`);
-                     head     = the expert's `encoder_q` / `encoder` output: max + mean over time, and `fc` where the wrapper has one.
+                     head     = the expert's `encoder_q` / `encoder` output: max + mean over time, and `fc` where the wrapper has one;
+                     x1 x2 x3 = the time means of the three conv blocks' pooled outputs ([N, 2048 / 1024 / 512] at 64 mels), the
+                                tensors DeLoRes-M puts its Barlow heads on and UnFuSeD distils into - whatever the config's
+                                `return_all_layers` says.
   ASTModel           backbone = the mean over the patch tokens before `fc` (`ast_work.py:229`), base224 and mvit alike;
                      head     = the `fc` output, i.e. the module's own forward.
 The token mean is `ctx.pooled` of the engines' forward: nothing an existing call returns changes.
@@ -21,7 +24,8 @@ import torch.nn.functional as F
 from src.utils import extract_window
 
 WINDOWS = ("center", "random")
-LAYERS = ("backbone", "head")
+LAYERS = ("backbone", "head", "x1", "x2", "x3")
+CONV_LAYERS = ("x1", "x2", "x3")
 _BASES = ("AudioNTT2020Task6", "ASTModel")
 
 
@@ -64,15 +68,20 @@ def _resolve(model):
 
 
 class Embedder:
-    """`Embedder(expert_or_encoder, layer="backbone"|"head", precision=None)`; `embedder(x)` maps a front-end batch
-    [B, 1, F, T] to float32 [B, d].  precision: "fp32" / "bf16" for the conv encoder (None = the module's own)."""
+    """`Embedder(expert_or_encoder, layer="backbone"|"head"|"x1"|"x2"|"x3", precision=None)`; `embedder(x)` maps a front-end
+    batch [B, 1, F, T] to float32 [B, d].  layer may be a tuple / list of names: `embedder(x)` is then a dict name -> [B, d]
+    from one pass.  precision: "fp32" / "bf16" for the conv encoder (None = the module's own)."""
 
     def __init__(self, model, layer="backbone", precision=None, input_shape=None):
-        if layer not in LAYERS:
-            raise ValueError(f"layer must be one of {LAYERS}")
+        self.multi = not isinstance(layer, str)
+        self.layers = tuple(layer) if self.multi else (layer,)
+        if not self.layers or any(l not in LAYERS for l in self.layers) or len(set(self.layers)) != len(self.layers):
+            raise ValueError(f"layer must be one of {LAYERS}, or a tuple of distinct ones")
         self.model, self.layer = model, layer
         self.wrapper, self.base = _resolve(model)
         self.kind = repr(self.base)
+        if self.kind != "AudioNTT2020Task6" and any(l in CONV_LAYERS for l in self.layers):
+            raise ValueError(f"layers {CONV_LAYERS} are the conv blocks of AudioNTT2020Task6; {self.kind} has none")
         self.precision = precision
         self.input_shape = input_shape
         self._front = None
@@ -93,21 +102,43 @@ class Embedder:
                 self._front = lambda waves: fb(waves.cuda().float(), None, tdim, mean=AUDIOSET_MEAN, std=AUDIOSET_STD, skip_norm=False)
         return self._front
 
+    def _base_all(self, x):
+        """(x1, x2, x3, h) of the conv encoder, whatever its `return_all_layers`; the flag is put back."""
+        own = self.base.return_all_layers
+        self.base.return_all_layers = True
+        try:
+            return self.base(x)
+        finally:
+            self.base.return_all_layers = own
+
     def _forward(self, x):
+        """-> {name: tensor} for self.layers.  One encoder forward serves every layer taken from the base encoder; `head` of a
+        wrapper with layers of its own is the wrapper's forward."""
+        out = {}
         if self.kind == "ASTModel":
             b = self.base
-            out, c = b.engine_forward(b.param_dict(), b.weight_shadow(), x.float().contiguous(), b.cfg, need_ctx=True)
-            return out if self.layer == "head" else c.pooled
-        if self.layer == "backbone":
-            from src.downstream.downstream_encoder import MeanTFn
-            h = self.base(x)
-            return MeanTFn.apply(h[-1] if isinstance(h, tuple) else h)
-        if self.wrapper is self.base:
-            from src.functional import MaxMeanFn
-            h = self.base(x)
-            return MaxMeanFn.apply(h[-1] if isinstance(h, tuple) else h)
-        y = self.wrapper(x)
-        return y[0] if isinstance(y, tuple) else y
+            y, c = b.engine_forward(b.param_dict(), b.weight_shadow(), x.float().contiguous(), b.cfg, need_ctx=True)
+            for l in self.layers:
+                out[l] = y if l == "head" else c.pooled
+            return out
+        head_is_wrapper = self.wrapper is not self.base
+        if any(l != "head" or not head_is_wrapper for l in self.layers):
+            if any(l in CONV_LAYERS for l in self.layers):
+                x1, x2, x3, h = self._base_all(x)
+                out.update({l: t for l, t in (("x1", x1), ("x2", x2), ("x3", x3)) if l in self.layers})
+            else:
+                h = self.base(x)
+                h = h[-1] if isinstance(h, tuple) else h
+            if "backbone" in self.layers:
+                from src.downstream.downstream_encoder import MeanTFn
+                out["backbone"] = MeanTFn.apply(h)
+            if "head" in self.layers and not head_is_wrapper:
+                from src.functional import MaxMeanFn
+                out["head"] = MaxMeanFn.apply(h)
+        if "head" in self.layers and head_is_wrapper:
+            y = self.wrapper(x)
+            out["head"] = y[0] if isinstance(y, tuple) else y
+        return out
 
     @torch.no_grad()
     def __call__(self, x):
@@ -119,7 +150,8 @@ class Embedder:
             from src import _native as N
             self.base.precision = {"fp32": N.F32, "bf16": N.BF16}.get(self.precision, self.precision)
         try:
-            return self._forward(x).float()
+            out = {l: t.float() for l, t in self._forward(x).items()}
+            return {l: out[l] for l in self.layers} if self.multi else out[self.layer]
         finally:
             if own is not None:
                 self.base.precision = own
@@ -129,7 +161,8 @@ class Embedder:
 
 @torch.no_grad()
 def extract_embeddings(embedder, files, batch_size=64, window="center", duration=1.0, pcm=False):
-    """files: paths (WAV / .npy, any rate) -> float32 [N, d] on the device, in file order.  duration in seconds.
+    """files: paths (WAV / .npy, any rate) -> float32 [N, d] on the device, in file order (a dict name -> [N, d] when the
+    embedder takes several layers: one pass over the files).  duration in seconds.
     pcm: ship the windows in the files' own sample formats and convert on the GPU (conv encoders; `PcmBatch`)."""
     from src.dataset.upstream_dataset import load_audio
     if window not in WINDOWS:
@@ -154,7 +187,10 @@ def extract_embeddings(embedder, files, batch_size=64, window="center", duration
         n = len(clips)
         if embedder.kind == "ASTModel" and n % 2:            # the transformer engines take batch * tokens in multiples of 8
             batch = torch.cat([batch, batch[-1:]])
-        out.append(embedder(front(batch))[:n])
+        e = embedder(front(batch))
+        out.append({l: t[:n] for l, t in e.items()} if embedder.multi else e[:n])
+    if embedder.multi:
+        return {l: torch.cat([o[l] for o in out]) for l in embedder.layers}
     return torch.cat(out)
 
 

@@ -489,6 +489,29 @@ int audiossl_knn_topk(const void* q, const void* bank, int Nq, long Nb, int D, i
 int audiossl_knn_vote(const float* top_sim, const int* top_idx, const long long* bank_label, int Nq, int k, long Nb,
                       float inv_t, long long* pred, float* conf, void* stream);
 
+/* ---- K21 centred kernel alignment between two feature sets of the same n clips (csrc/cka.hip): `linear_CKA` / `kernel_CKA`
+ * of extras/CKA.py:1-60, without its n x n matrices.  x [n][p], y [n][q] row-major fp32, row i of both from the same clip;
+ * 2 <= n <= 65536, p and q multiples of 4 in [4, 4096] (pad with zero columns: they change no Gram entry).  Gram tiles on the
+ * fp32-input MFMA, reduced where they are formed: sum(HKH * HLH) = S_KL - (2/n) sum_i k_i l_i + k l / n^2 (k_i, l_i row sums,
+ * k, l totals), fp64 sums folded in a fixed order, so two calls agree bit for bit.  Nothing synchronises with the host.
+ * cka_workspace (host): bytes of `workspace` for cka_sigma2 and cka_hsic, non-decreasing in n; it needs no clearing.
+ * cka_center: out = x - column mean (fp64 means, one rounding); changes neither the centred linear Gram nor any distance.
+ *   cka_sigma2 and cka_hsic take the data as given.
+ * cka_sigma2: sigma2[0] = median of the non-zero d_ij = max((g_ii + g_jj) - 2 g_ij, 0) over j > i (equal to the median over the
+ *   full symmetric matrix, `np.median(KX[KX != 0])`): the mean of the order statistics (M-1)/2 and M/2 of the kernel's own fp32
+ *   distances, exact (radix select over their bit patterns, three sweeps); count[0] (optional) = M.  M = 0 gives NaN.
+ * cka_hsic: kernel 0 = linear (K = X X^T), 1 = RBF (K_ij = exp(-d_ij / (2 sigma^2)), d_ii = 0, the coefficient -0.5 / sigma^2
+ *   formed in fp64 and rounded to fp32 once).  RBF takes EITHER sigma > 0 for both matrices (sigma2_x = sigma2_y = NULL) OR both
+ *   device pointers sigma2_x, sigma2_y (as cka_sigma2 wrote them) with sigma = 0.  out[8] (device, fp64) = {cka, hsic_xy,
+ *   hsic_xx, hsic_yy, S_kl, S_kk, S_ll, 0}; rowsum_k / rowsum_l [n] fp64 are optional outputs (NULL = not wanted). */
+int audiossl_cka_workspace(int n, int p, int q, long* bytes);
+int audiossl_cka_center(const float* x, int n, int p, float* out, void* stream);
+int audiossl_cka_sigma2(const float* x, int n, int p, double* sigma2, long long* count, void* workspace,
+                        long workspace_bytes, void* stream);
+int audiossl_cka_hsic(const float* x, const float* y, int n, int p, int q, int kernel, double sigma,
+                      const double* sigma2_x, const double* sigma2_y, double* out, double* rowsum_k,
+                      double* rowsum_l, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- row softmax: nn.Softmax(dim=1) closing SLICER's cluster projector (src/upstream/slicer/upstream_encoder.py:15-20);
  * fp32 [M][C]; bwd: gx = y * (gy - sum_c gy*y). */
 int audiossl_softmax_rows_fwd(const float* x, float* y, int M, int C, void* stream);
