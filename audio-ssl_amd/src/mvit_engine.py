@@ -18,7 +18,7 @@ import torch
 
 from src import _native as N
 from src import engine as E
-from src.vit_engine import ViTCtx, _cast, _ln, _wgrad
+from src.vit_engine import ViTCtx, _cast, _ln, _wgrad, fc_backward
 
 BF = N.BF16
 
@@ -304,17 +304,7 @@ def mvit_backward(c, P, W, G, dout):
     Ntok, Cl = c.Ntok, c.Cl
     Ml = B * Ntok
     dev = dout.device
-    out_dim = W["fc.weight"].shape[0]
-    Bp = (B + 7) // 8 * 8
-    dob = torch.zeros(Bp, out_dim, dtype=torch.bfloat16, device=dev)
-    dob[:B].copy_(dout)
-    pooled = c.pooled
-    if Bp != B:
-        pooled = torch.zeros(Bp, Cl, dtype=torch.bfloat16, device=dev)
-        pooled[:B].copy_(c.pooled)
-    _wgrad(dob, pooled, G["fc.weight"], Bp, out_dim, Cl)
-    E.colsum_add(N.F32, dout.float().contiguous(), B, out_dim, G["fc.bias"])
-    dpool = E.linear_bwd_x(BF, dob, W["fc.weight"], Bp, out_dim, Cl, out_f32=1)
+    dpool = fc_backward(dout, c.pooled, W["fc.weight"], G, B, Cl)
     dYf = torch.empty(Ml, Cl, dtype=torch.float32, device=dev)
     N.call("tile_rows", dpool, dYf, Ml, B, Ntok, 1.0 / Ntok, Cl)
     if cfg["final_norm"]:

@@ -152,6 +152,34 @@ def block_backward(k, P, W, G, p, dX, B, Ntok, C, H):
     N.call("layernorm_bwd", dY1, k.X1, k.mu1, k.rs1, P[p + "norm1.weight"], dX, G[p + "norm1.weight"], G[p + "norm1.bias"], M, C)
 
 
+def fc_backward(dout, pooled, Wfc, G, B, C):
+    """Backward of the closing Linear(C, out_dim) on the pooled tokens: G["fc.weight"], G["fc.bias"] += ; -> dpool fp32 [Bp, C].
+    The kernels vectorise the class axis by 8 (GEMM) / 64 (column sums): an out_dim that is no multiple of 64 (a tagging head:
+    527 AudioSet classes) is zero-padded for the three launches, as `functional.LinearFn` does; a multiple runs as it always did."""
+    dev = dout.device
+    out_dim = Wfc.shape[0]
+    Op = (out_dim + 63) // 64 * 64
+    Bp = (B + 7) // 8 * 8                                    # the weight-gradient GEMM contracts over rows: multiple of 8
+    d32 = dout.float().contiguous()
+    dob = torch.zeros(Bp, Op, dtype=torch.bfloat16, device=dev)
+    dob[:B, :out_dim].copy_(dout)
+    if Bp != B:
+        padded = torch.zeros(Bp, C, dtype=torch.bfloat16, device=dev)
+        padded[:B].copy_(pooled)
+        pooled = padded
+    if Op == out_dim:
+        _wgrad(dob, pooled, G["fc.weight"], Bp, out_dim, C)
+        E.colsum_add(N.F32, d32, B, out_dim, G["fc.bias"])
+        return E.linear_bwd_x(BF, dob, Wfc, Bp, out_dim, C, out_f32=1)
+    gw = torch.zeros(Op, C, dtype=torch.float32, device=dev)
+    gb = torch.zeros(Op, dtype=torch.float32, device=dev)
+    _wgrad(dob, pooled, gw, Bp, Op, C)
+    E.colsum_add(N.F32, torch.nn.functional.pad(d32, (0, Op - out_dim)), B, Op, gb)
+    G["fc.weight"].add_(gw[:out_dim])
+    G["fc.bias"].add_(gb[:out_dim])
+    return E.linear_bwd_x(BF, dob, torch.nn.functional.pad(Wfc, (0, 0, 0, Op - out_dim)), Bp, Op, C, out_f32=1)
+
+
 def vit_backward(c, P, W, G, dout):
     """dout [B, out_dim] fp32 -> accumulates every parameter gradient into G (fp32, keyed like P)."""
     cfg = c.cfg
@@ -159,17 +187,7 @@ def vit_backward(c, P, W, G, dout):
     C, H, depth = cfg["embed_dim"], cfg["num_heads"], cfg["depth"]
     dev = dout.device
     scale = 1.0 / math.sqrt(C // H)
-    out_dim = W["fc.weight"].shape[0]
-    Bp = (B + 7) // 8 * 8                                    # the weight-gradient GEMM contracts over rows: multiple of 8
-    dob = torch.zeros(Bp, out_dim, dtype=torch.bfloat16, device=dev)
-    dob[:B].copy_(dout)
-    pooled = c.pooled
-    if Bp != B:
-        pooled = torch.zeros(Bp, C, dtype=torch.bfloat16, device=dev)
-        pooled[:B].copy_(c.pooled)
-    _wgrad(dob, pooled, G["fc.weight"], Bp, out_dim, C)
-    E.colsum_add(N.F32, dout.float().contiguous(), B, out_dim, G["fc.bias"])
-    dpool = E.linear_bwd_x(BF, dob, W["fc.weight"], Bp, out_dim, C, out_f32=1)             # [Bp, C] fp32
+    dpool = fc_backward(dout, c.pooled, W["fc.weight"], G, B, C)                          # [Bp, C] fp32
     dYf = torch.empty(M, C, dtype=torch.float32, device=dev)         # mean over tokens backward: each token row gets dpool / Ntok
     N.call("tile_rows", dpool, dYf, M, B, Ntok, 1.0 / Ntok, C)
     dX = torch.zeros(M, C, dtype=torch.float32, device=dev)

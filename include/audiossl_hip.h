@@ -512,6 +512,34 @@ int audiossl_cka_hsic(const float* x, const float* y, int n, int p, int q, int k
                       const double* sigma2_x, const double* sigma2_y, double* out, double* rowsum_k,
                       double* rowsum_l, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- K22 audio tagging (multi-label downstream, csrc/tagging.hip): nn.BCEWithLogitsLoss (the "bce_logit" of
+ * `extras/mast_new/mast/mvit/models/losses.py:38`) on the multi-hot / mixed targets of `mast/dataloader.py:157-184` and the per-class metrics of
+ * `extras/mast_new/mast/utilities/stats.py:11-57` (sklearn's average_precision_score / roc_auc_score, class by class on the host
+ * there).
+ * bce_rows: logits, targets fp32 [N][C], targets in [0, 1] (soft after a mix).  loss_out[0] (one float32, written, not
+ *   accumulated) = mean over N*C of max(x,0) - x t + log1p(exp(-|x|)): fp32 terms, fp64 sum in a fixed order by one workgroup
+ *   (the entry point takes no scratch), no atomics - two calls agree bit for bit.  dlogits [N][C] fp32 (dtype 0) or bf16
+ *   (dtype 1) = (sigmoid(x) - t) / (N*C); NULL = forward only.  N >= 1, C >= 1, N*C <= 2^40.
+ * tagging_stats: scores fp32 [N][C] (finite; raw logits rank at least as finely as their sigmoid), targets uint8 [N][C]
+ *   (non-zero = positive).  Per class c:
+ *     npos[c]     = number of positives;
+ *     auc_num2[c] = sum over positives i of 2 #{negatives j: s_j < s_i} + #{negatives j: s_j == s_i}  (exact integer);
+ *     auc[c]      = auc_num2 / (2 npos nneg): roc_auc_score, ties at half credit (the ROC trapezoid over tie groups);
+ *     ap[c]       = (1/npos) sum over positives i of #{positives j: s_j >= s_i} / #{all j: s_j >= s_i}: average_precision_score
+ *                   (thresholds = distinct scores, a tie group's recall step at the precision after the whole group).
+ *   ap and auc are NaN for a class without a positive or without a negative (auc_num2 is then 0).  +0.0 and -0.0 are one tie
+ *   group.  No sort: integer pair counts of each class's positives against its column, then one fp64 sum per class in a fixed
+ *   order (no float atomics), so the outputs depend on the inputs alone.  Work ~ sum_c npos_c (N + npos_c) comparisons.
+ *   `workspace` (device, tagging_workspace bytes) holds the class-major copies, the compacted positives and the per-workgroup
+ *   partials; it needs no clearing.  1 <= N < 2^31, C >= 1, C * N <= 2^40 and C * ceil(N / 256) < 2^31; `scores` and
+ *   `workspace` 16-byte aligned.  Nothing synchronises with the host.
+ * tagging_workspace (host): bytes for tagging_stats, about 9 C N + 16 C ceil(N / 256), non-decreasing in N and in C. */
+int audiossl_bce_rows(int dtype, const float* logits, const float* targets, long N, int C, float* loss_out, void* dlogits,
+                      void* stream);
+int audiossl_tagging_workspace(long N, int C, long* bytes);
+int audiossl_tagging_stats(const float* scores, const unsigned char* targets, long N, int C, int* npos, long long* auc_num2,
+                           double* ap, double* auc, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- row softmax: nn.Softmax(dim=1) closing SLICER's cluster projector (src/upstream/slicer/upstream_encoder.py:15-20);
  * fp32 [M][C]; bwd: gx = y * (gy - sum_c gy*y). */
 int audiossl_softmax_rows_fwd(const float* x, float* y, int M, int C, void* stream);
