@@ -512,6 +512,39 @@ int audiossl_cka_hsic(const float* x, const float* y, int n, int p, int q, int k
                       const double* sigma2_x, const double* sigma2_y, double* out, double* rowsum_k,
                       double* rowsum_l, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- K23 power-iteration clustering on an exact nearest-neighbour graph (csrc/graph.hip): `make_graph`, `make_adjacencyW`,
+ * `run_pic` and `find_maxima_cluster` of extras/decar-v2/clustering.py:118-230 (faiss index, scipy csr_matrix and Python loops
+ * there).  Every workspace is device memory that needs no clearing; two calls on the same inputs agree bit for bit (no float
+ * atomics); nothing synchronises with the host.
+ * knn_graph_l2: x [n][d] row-major fp32 -> idx [n][k] int32, d2 [n][k] fp32: for each row i the k rows j != i with the smallest
+ *   d2_ij = max(0, (n_i + n_j) - 2 g_ij), in the order (d2 ascending, j ascending) - a strict total order, so heavy ties are
+ *   resolved the same way however the tiles are walked.  g_ij on the fp32-input MFMA, an fmaf chain over d in index order;
+ *   n_i = g_ii by the same chain, so a repeated row is at distance exactly 0.  Self is excluded by index: a duplicate row IS a
+ *   neighbour.  The n x n matrix is never stored.  1 <= k <= 64, k <= n - 1, d % 4 == 0 (pad with zero columns), 4 <= d <= 4096,
+ *   n k < 2^31; inputs finite.
+ * knn_graph_workspace (host): bytes for knn_graph_l2 (norms + per-split lists), non-decreasing in n and in k.
+ * pic_build: idx, d2 [n][k] as knn_graph_l2 wrote them (a row's entries distinct; an index outside [0, n) is dropped), sigma > 0 ->
+ *   CSR of W = A + A^T, A_ij = exp(-d2_ij / sigma^2) for j in row i's list, exponent and exp in fp64.  rowptr [n + 1], col and
+ *   w [2 n k] (capacity; nnz[0] entries are written), rows canonical: columns ascending, a mutual pair merged into one entry
+ *   a_ij + a_ji.  Any in-degree up to n - 1.  n k < 2^30.
+ * pic_power: v [n] fp64 = `iters` rounds of u = alpha W v + (1 - alpha) / n, v = u / sum(u), from v = 1 / n.  Row sums in column
+ *   order, the global sum in a fixed tree.  `cap` = entries col / w hold (rowptr is clamped to it, a column outside [0, n) is
+ *   skipped: a malformed matrix cannot make the kernels read out of bounds).
+ * pic_assign: parent(i) = the neighbour j maximising W_ij (v_j - v_i) among strictly positive values, ties to the smaller j,
+ *   else i; label[i] = number of its root among the roots in ascending node order, count[0] = number of roots.  Roots by
+ *   pointer doubling, ceil(log2 n) rounds.
+ * pic_workspace (host): bytes that serve pic_build (n, k), pic_power and pic_assign (n). */
+int audiossl_knn_graph_workspace(int n, int k, long* bytes);
+int audiossl_knn_graph_l2(const float* x, int n, int d, int k, int* idx, float* d2, void* workspace, long workspace_bytes,
+                          void* stream);
+int audiossl_pic_workspace(int n, int k, long* bytes);
+int audiossl_pic_build(const int* idx, const float* d2, int n, int k, double sigma, int* rowptr, int* col, double* w, int* nnz,
+                       void* workspace, long workspace_bytes, void* stream);
+int audiossl_pic_power(const int* rowptr, const int* col, const double* w, int n, long cap, double alpha, int iters, double* v,
+                       void* workspace, long workspace_bytes, void* stream);
+int audiossl_pic_assign(const int* rowptr, const int* col, const double* w, const double* v, int n, long cap, int* label,
+                        int* count, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- K22 audio tagging (multi-label downstream, csrc/tagging.hip): nn.BCEWithLogitsLoss (the "bce_logit" of
  * `extras/mast_new/mast/mvit/models/losses.py:38`) on the multi-hot / mixed targets of `mast/dataloader.py:157-184` and the per-class metrics of
  * `extras/mast_new/mast/utilities/stats.py:11-57` (sklearn's average_precision_score / roc_auc_score, class by class on the host
