@@ -31,7 +31,7 @@
 // atomics: every workgroup writes its partials to the workspace, cka_finalize_kernel folds them in a fixed order, so two
 // runs agree bit for bit.  The kernels initialise whatever they read; the workspace needs no clearing by the caller.
 // The full square is swept (K and L are symmetric; the triangle would halve a cost of milliseconds).
-#include "common.h"
+#include "topk.h"          // plan_splits, TARGET_WG
 
 namespace {
 
@@ -39,7 +39,6 @@ constexpr int RT = 64;               // owned rows per workgroup
 constexpr int CT = 128;              // walked columns per tile
 constexpr int KC = 32;               // feature chunk per staging step
 constexpr int RP = KC + 4;           // staging pitch (floats): 144-byte rows, 16-byte aligned float4 fragments
-constexpr int TARGET_WG = 512;       // two workgroups per CU on 256 CUs
 constexpr int MIN_TILES = 2;         // column tiles per split at least
 constexpr int NBIN = 2048;           // radix-select bins per pass (11 + 11 + 10 bits)
 constexpr int MAX_N = 65536;
@@ -57,18 +56,16 @@ struct CkaPlan {
     long off_gx, off_gy, off_rk, off_rl, off_s, off_hist, off_state, bytes;
 };
 
-// Splits as in knn.hip: enough workgroups to fill the chip when there are few row blocks, MIN_TILES column tiles per split
-// at least.  The workspace figure uses row_blocks + TARGET_WG >= row_blocks * splits, so it grows with n.
+// Splits (plan_splits in topk.h): MIN_TILES column tiles each at least.  The workspace figure uses row_blocks + TARGET_WG >=
+// row_blocks * splits, so it grows with n.
 bool cka_plan(long n, CkaPlan& p) {
     if (!(n >= 2 && n <= MAX_N)) return false;
     p.row_blocks = (int)((n + RT - 1) / RT);
     p.col_tiles = (int)((n + CT - 1) / CT);
     p.n_pad = (long)p.row_blocks * RT;
-    const int max_splits = p.col_tiles / MIN_TILES > 0 ? p.col_tiles / MIN_TILES : 1;
-    int splits = (TARGET_WG + p.row_blocks - 1) / p.row_blocks;
-    if (splits > max_splits) splits = max_splits;
-    p.tiles_per_split = (p.col_tiles + splits - 1) / splits;
-    p.splits = (p.col_tiles + p.tiles_per_split - 1) / p.tiles_per_split;          // no empty split
+    const SplitPlan sp = plan_splits(p.row_blocks, p.col_tiles, MIN_TILES);
+    p.splits = sp.splits;
+    p.tiles_per_split = sp.tiles_per_split;
     const long wg_bound = (long)p.row_blocks + TARGET_WG;
     long o = 0;
     p.off_gx = o;    o += p.n_pad * 4;

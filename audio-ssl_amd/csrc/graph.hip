@@ -11,11 +11,10 @@
 //   holds feature 8 g + 2 s + h: the chain runs over d in INDEX order, graph_norm_kernel runs the same chain for n_i = g_ii,
 //   and d2_ij = max(0, (n_i + n_j) - 2 g_ij) is exactly 0 wherever row j repeats row i.  Self is excluded by INDEX, so a
 //   duplicate row is a legitimate neighbour at distance 0.
-//   The n x n matrix is never stored; the reduction is knn.hip's: the 64 x 128 tile is dumped to LDS over the dead staging
-//   buffers, wave w scans rows 16w..16w+15 with one ballot of "beats the row's current k-th entry", and only then pulls the
-//   row's sorted list (k <= 64: one entry per lane) into registers and inserts.  Order: (d2 ascending, j ascending), a strict
-//   total order used in every comparison, so the result does not depend on how tiles or splits deliver candidates.  Few rows:
-//   the walked rows are split over blockIdx.y, every split writes its k best to the workspace, a merge kernel folds them.
+//   The n x n matrix is never stored: the 64 x 128 tile is dumped to LDS over the dead staging buffers and wave w scans rows
+//   16w..16w+15 with the streaming selector of topk.h (k <= 64: the one-slot list), order (d2 ascending, j ascending).  Few
+//   rows: the walked rows are split over blockIdx.y, every split writes its k best to the workspace, topk_merge_kernel folds
+//   them.
 //
 // pic_build: CSR of W = A + A^T, A_ij = exp(-d2_ij / sigma^2) for j in row i's list (fp64 from the fp32 distance): count
 //   in-degrees (integer atomics), scan, scatter (out-edges at fixed slots, in-edges through an integer cursor), then each
@@ -28,8 +27,7 @@
 //   roots numbered in ascending node order (the reference's `cluster_ids`).
 //
 // No float atomics, no grid-wide barriers, plain launches only; the kernels initialise whatever they read of the workspace.
-#include "common.h"
-#include <limits.h>
+#include "topk.h"
 
 namespace {
 
@@ -41,40 +39,8 @@ constexpr int SP = BT + 4;           // Gram tile pitch (floats): 528-byte rows,
 constexpr int KP = 64;               // list slots per row: one per lane
 constexpr int TILE_BYTES = QT * SP * 4;                  // 33,792 >= the staging buffers' (QT + BT) * RP * 4 = 27,648
 constexpr int LDS_BYTES = TILE_BYTES + QT * KP * 8;      // + the rows' lists
-constexpr int TARGET_WG = 512;       // two workgroups per CU on 256 CUs
 constexpr int MAX_D = 4096;
 static_assert(TILE_BYTES >= (QT + BT) * RP * 4, "the Gram tile lies over the staging buffers");
-
-// strict total order on (squared distance, row): smaller distance first, smaller row first among equals
-__device__ __forceinline__ bool closer(float a, int ia, float b, int ib) { return a < b || (a == b && ia < ib); }
-
-// A row's sorted list spread over one wave: slot = lane.  Empty slots hold (+inf, INT_MAX).
-struct NearList {
-    float v;
-    int i;
-    __device__ __forceinline__ void kth(int k, float& tv, int& ti) const { tv = __shfl(v, k - 1, 64); ti = __shfl(i, k - 1, 64); }
-};
-
-// One candidate per lane (cv, ci, valid) folded into the list; k is wave-uniform.  Everything after the first ballot is
-// wave-uniform control flow.
-__device__ __forceinline__ void fold(NearList& L, float cv, int ci, bool valid, int k, int lane) {
-    float tv; int ti;
-    L.kth(k, tv, ti);
-    unsigned long long m = __ballot(valid && closer(cv, ci, tv, ti));
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float c = __shfl(cv, src, 64);
-        const int cidx = __shfl(ci, src, 64);
-        if (!closer(c, cidx, tv, ti)) continue;                    // an earlier insertion raised the bar
-        const int pos = __popcll(__ballot(closer(L.v, L.i, c, cidx)));   // entries ahead of the candidate = its slot (< k)
-        const float pv = __shfl_up(L.v, 1, 64);
-        const int pi = __shfl_up(L.i, 1, 64);
-        if (lane == pos) { L.v = c; L.i = cidx; }
-        else if (lane > pos) { L.v = pv; L.i = pi; }
-        L.kth(k, tv, ti);
-    }
-}
 
 struct GraphArgs {
     const float* x;      // [n][d]
@@ -111,8 +77,7 @@ __global__ __launch_bounds__(256) void graph_topk_kernel(GraphArgs a) {
     const long q0 = (long)blockIdx.x * QT;
     const int n = a.n, d = a.d, k = a.k;
 
-    for (int e = tid; e < QT * KP; e += 256) { Lv[e] = INFINITY; Li[e] = INT_MAX; }
-    // (the first barrier of the tile loop orders this against the scans; every split owns at least one tile)
+    topk_lds_init<QT, KP, DistAscending>(Lv, Li);
 
     const int t0 = blockIdx.y * a.tiles_per_split;
     const int t1 = min(t0 + a.tiles_per_split, a.tiles);
@@ -181,53 +146,16 @@ __global__ __launch_bounds__(256) void graph_topk_kernel(GraphArgs a) {
         const bool ok0 = r0 < n, ok1 = r1 < n;
         const int i0 = (int)r0, i1 = (int)r1;
         const float nj0 = ok0 ? a.gn[r0] : 0.f, nj1 = ok1 ? a.gn[r1] : 0.f;
-        for (int qq = 0; qq < QT / 4; ++qq) {
-            const int q = w * (QT / 4) + qq;
+        topk_lds_scan<QT, KP, DistAscending>(Lv, Li, k, q0, n, lane, w, [&](int q, int h) {
             const long gq = q0 + q;
-            if (gq >= n) break;                                      // wave-uniform; no barrier inside this loop
             const float ni = a.gn[gq];
-            const float d0 = fmaxf((ni + nj0) - 2.f * St[q * SP + lane], 0.f);
-            const float d1 = fmaxf((ni + nj1) - 2.f * St[q * SP + 64 + lane], 0.f);
-            const bool c0 = ok0 && r0 != gq, c1 = ok1 && r1 != gq;   // self leaves by index, not by value
-            const float tv = Lv[q * KP + k - 1];
-            const int ti = Li[q * KP + k - 1];
-            if (__ballot((c0 && closer(d0, i0, tv, ti)) || (c1 && closer(d1, i1, tv, ti))) == 0ull) continue;
-            NearList L;
-            L.v = Lv[q * KP + lane]; L.i = Li[q * KP + lane];
-            fold(L, d0, i0, c0, k, lane);
-            fold(L, d1, i1, c1, k, lane);
-            Lv[q * KP + lane] = L.v; Li[q * KP + lane] = L.i;
-        }
+            const float dd = fmaxf((ni + (h ? nj1 : nj0)) - 2.f * St[q * SP + 64 * h + lane], 0.f);
+            return TopCand{dd, h ? i1 : i0, h ? ok1 && r1 != gq : ok0 && r0 != gq};   // self leaves by index, not by value
+        });
     }
 
-    // a wave's 16 lists are its own: no barrier between its last scan and this
-    float* ov = a.out_v + (long)blockIdx.y * a.split_stride;
-    int* oi = a.out_i + (long)blockIdx.y * a.split_stride;
-    for (int qq = 0; qq < QT / 4; ++qq) {
-        const int q = w * (QT / 4) + qq;
-        const long gq = q0 + q;
-        if (gq >= n) break;
-        if (lane < k) { ov[gq * k + lane] = Lv[q * KP + lane]; oi[gq * k + lane] = Li[q * KP + lane]; }
-    }
-}
-
-// one wave per row: the splits' lists [splits][n][k] -> the k best.  Slots a split could not fill carry INT_MAX.
-__global__ __launch_bounds__(256) void graph_merge_kernel(const float* __restrict__ wv, const int* __restrict__ wi, int splits,
-                                                          long split_stride, int n, int k, float* __restrict__ d2,
-                                                          int* __restrict__ idx) {
-    const int lane = threadIdx.x & 63;
-    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= n) return;                                              // whole waves leave; no barrier below
-    NearList L;
-    L.v = INFINITY; L.i = INT_MAX;
-    for (int s = 0; s < splits; ++s) {
-        const long base = (long)s * split_stride + q * k;
-        const bool in = lane < k;
-        const float cv = in ? wv[base + lane] : 0.f;
-        const int ci = in ? wi[base + lane] : INT_MAX;
-        fold(L, cv, ci, in && ci != INT_MAX, k, lane);
-    }
-    if (lane < k) { d2[q * k + lane] = L.v; idx[q * k + lane] = L.i; }
+    topk_lds_write<QT, KP>(Lv, Li, k, q0, n, lane, w, a.out_v + (long)blockIdx.y * a.split_stride,
+                           a.out_i + (long)blockIdx.y * a.split_stride);
 }
 
 struct GraphPlan {
@@ -236,19 +164,17 @@ struct GraphPlan {
     long n_pad, ws_bytes;
 };
 
-// Splits as in knn.hip: enough workgroups to fill the chip when there are few row tiles, at least four walked tiles per split.
-// The workspace figure is a bound on splits * n * k * 8 that grows with n and with k.
+// Splits (plan_splits): at least four walked tiles each.  The workspace figure is a bound on splits * n * k * 8 that grows
+// with n and with k.
 bool graph_plan(int n, int k, GraphPlan& p) {
     if (!(n >= 2 && k >= 1 && k <= KP && k <= n - 1 && (long)n * k < (1L << 31))) return false;
     p.q_tiles = ((long)n + QT - 1) / QT;
     p.tiles = (int)(((long)n + BT - 1) / BT);
-    const long max_splits = p.tiles / 4 > 0 ? p.tiles / 4 : 1;
-    long splits = (TARGET_WG + p.q_tiles - 1) / p.q_tiles;
-    if (splits > max_splits) splits = max_splits;
-    p.tiles_per_split = (int)((p.tiles + splits - 1) / splits);
-    p.splits = (p.tiles + p.tiles_per_split - 1) / p.tiles_per_split;             // no empty split
+    const SplitPlan sp = plan_splits(p.q_tiles, p.tiles, 4);
+    p.splits = sp.splits;
+    p.tiles_per_split = sp.tiles_per_split;
     p.n_pad = p.q_tiles * QT;
-    const long a = p.q_tiles + TARGET_WG - 1, b = p.q_tiles * max_splits;
+    const long a = p.q_tiles + TARGET_WG - 1, b = p.q_tiles * sp.max_splits;
     p.ws_bytes = p.n_pad * 4 + (a < b ? a : b) * QT * (long)k * 8;
     return true;
 }
@@ -495,13 +421,7 @@ extern "C" int audiossl_knn_graph_l2(const float* x, int n, int d, int k, int* i
     ASSL_REQUIRE(workspace_bytes >= p.ws_bytes);
     if (!ASSL_ALIGNED16(x) || !ASSL_ALIGNED16(workspace)) return ASSL_EALIGN;
     hipStream_t s = S_(stream);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(graph_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                LDS_BYTES) != hipSuccess)
-            return ASSL_ELAUNCH;
-        attr_set = true;
-    }
+    if (!allow_dynamic_lds<graph_topk_kernel>(LDS_BYTES)) return ASSL_ELAUNCH;
     float* gn = static_cast<float*>(workspace);
     GraphArgs a;
     a.x = x; a.gn = gn;
@@ -515,8 +435,8 @@ extern "C" int audiossl_knn_graph_l2(const float* x, int n, int d, int k, int* i
     hipLaunchKernelGGL(graph_norm_kernel, GRID1(n), dim3(256), 0, s, x, n, d, gn);
     hipLaunchKernelGGL(graph_topk_kernel, dim3((unsigned)p.q_tiles, (unsigned)p.splits), dim3(256), LDS_BYTES, s, a);
     if (p.splits > 1)
-        hipLaunchKernelGGL(graph_merge_kernel, dim3((unsigned)(((long)n + 3) / 4)), dim3(256), 0, s, wv, wi, p.splits, a.split_stride, n, k,
-                           d2, idx);
+        hipLaunchKernelGGL((topk_merge_kernel<KP, DistAscending>), dim3((unsigned)(((long)n + 3) / 4)), dim3(256), 0, s, wv, wi, p.splits,
+                           a.split_stride, n, k, d2, idx);
     ASSL_LAUNCH_CHECK();
 }
 

@@ -7,19 +7,13 @@
 //   * A workgroup (4 waves) owns 64 queries and walks a run of 128-row bank tiles.  Per tile: a plain LDS-staged GEMM over D
 //     in chunks of 64 (next chunk's global loads in flight during the MFMAs), similarities TRANSPOSED as in attention.hip
 //     (A = bank rows, B = queries: a lane's column is a query, its 16 registers are bank rows).
-//   * The 64 x 128 fp32 tile is dumped to LDS over the dead staging buffers; wave w then scans queries 16w..16w+15: one ballot
-//     of "beats the query's current k-th entry" over the 128 values.  Almost always the ballot is empty once the lists have
-//     warmed up (a query sees about k ln(Nb / k) insertions in all).  Otherwise the query's sorted list (k <= 128: one or two
-//     entries per lane) is pulled into registers and the candidates are inserted one at a time: position = popcount of a
-//     ballot, shift = one lane rotation.
-//   * Order: (sim descending, bank row ascending) is a strict total order on candidates, every comparison uses it, so the
-//     result does not depend on the order in which tiles, waves or splits deliver candidates.
-//   * Few queries: the bank is split over blockIdx.y; every split writes its k best per query to the workspace and a merge
-//     kernel (one wave per query, the same register list) folds them.  With one split the lists go straight to the output.
+//   * The 64 x 128 fp32 tile is dumped to LDS over the dead staging buffers; wave w then scans queries 16w..16w+15 with the
+//     streaming selector of topk.h (k <= 128: a one- or two-slot list per query), order (sim descending, bank row ascending).
+//   * Few queries: the bank is split over blockIdx.y; every split writes its k best per query to the workspace and
+//     topk_merge_kernel folds them.  With one split the lists go straight to the output.
 //
 // knn_vote: one wave per query, k x k label comparison (labels are compared, never used as an index).
-#include "common.h"
-#include <limits.h>
+#include "topk.h"
 
 namespace {
 
@@ -29,61 +23,9 @@ constexpr int KC = 64;              // D chunk per staging step
 constexpr int RP = KC + 8;          // staging pitch (elements): 144-byte rows, 16-byte aligned fragments
 constexpr int SP = BT + 4;          // similarity tile pitch (floats): 528-byte rows, 16-byte aligned float4 stores
 constexpr int TILE_BYTES = QT * SP * 4;                 // 33,792 >= the staging buffers' (QT + BT) * RP * 2 = 27,648
-constexpr int TARGET_WG = 512;      // two workgroups per CU on 256 CUs
 static_assert(TILE_BYTES >= (QT + BT) * RP * 2, "the similarity tile lies over the staging buffers");
 
 constexpr size_t knn_lds_bytes(int KP) { return (size_t)TILE_BYTES + (size_t)QT * KP * 8; }
-
-// strict total order on (similarity, bank row): larger similarity first, smaller row first among equals
-__device__ __forceinline__ bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
-// A query's sorted list spread over one wave: slot s * 64 + lane.  Empty slots hold (-inf, INT_MAX).
-template <int KP> struct TopList {
-    float v[KP / 64];
-    int i[KP / 64];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int s = 0; s < KP / 64; ++s) { v[s] = -INFINITY; i[s] = INT_MAX; }
-    }
-    __device__ __forceinline__ void kth(int k, float& tv, int& ti) const {
-        if (KP == 64 || k <= 64) { tv = __shfl(v[0], k - 1, 64); ti = __shfl(i[0], k - 1, 64); }
-        else                     { tv = __shfl(v[KP / 64 - 1], k - 65, 64); ti = __shfl(i[KP / 64 - 1], k - 65, 64); }
-    }
-};
-
-// One candidate per lane (cv, ci, valid) folded into the list; k is wave-uniform.  Everything after the first ballot is
-// wave-uniform control flow.
-template <int KP>
-__device__ __forceinline__ void fold(TopList<KP>& L, float cv, int ci, bool valid, int k, int lane) {
-    constexpr int NS = KP / 64;
-    float tv; int ti;
-    L.kth(k, tv, ti);
-    unsigned long long m = __ballot(valid && better(cv, ci, tv, ti));
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float c = __shfl(cv, src, 64);
-        const int cidx = __shfl(ci, src, 64);
-        if (!better(c, cidx, tv, ti)) continue;                    // an earlier insertion raised the bar
-        int pos = 0;                                               // entries ahead of the candidate = its slot (< k)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) pos += __popcll(__ballot(better(L.v[s], L.i[s], c, cidx)));
-        float carry_v = 0.f; int carry_i = 0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            float pv = __shfl_up(L.v[s], 1, 64);
-            int pi = __shfl_up(L.i[s], 1, 64);
-            const float last_v = __shfl(L.v[s], 63, 64);
-            const int last_i = __shfl(L.i[s], 63, 64);
-            if (lane == 0) { pv = carry_v; pi = carry_i; }        // slot 0 is never > pos: the s == 0 carry is unused
-            const int slot = s * 64 + lane;
-            if (slot == pos) { L.v[s] = c; L.i[s] = cidx; }
-            else if (slot > pos) { L.v[s] = pv; L.i[s] = pi; }
-            carry_v = last_v; carry_i = last_i;
-        }
-        L.kth(k, tv, ti);
-    }
-}
 
 struct KnnArgs {
     const bf16* q;       // [Nq][D]
@@ -108,8 +50,7 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnArgs a) {
     const long q0 = (long)blockIdx.x * QT;
     const int D = a.D, k = a.k;
 
-    for (int e = tid; e < QT * KP; e += 256) { Lv[e] = -INFINITY; Li[e] = INT_MAX; }
-    // (the first barrier of the tile loop orders this against the scans; every split owns at least one tile)
+    topk_lds_init<QT, KP, SimDescending>(Lv, Li);
 
     const int t0 = blockIdx.y * a.tiles_per_split;
     const int t1 = min(t0 + a.tiles_per_split, a.bank_tiles);
@@ -172,61 +113,13 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnArgs a) {
         const long r0 = b0 + lane, r1 = b0 + 64 + lane;
         const bool ok0 = r0 < a.Nb, ok1 = r1 < a.Nb;
         const int i0 = (int)r0, i1 = (int)r1;
-        for (int qq = 0; qq < QT / 4; ++qq) {
-            const int q = w * (QT / 4) + qq;
-            const float v0 = St[q * SP + lane], v1 = St[q * SP + 64 + lane];
-            const float tv = Lv[q * KP + k - 1];
-            const int ti = Li[q * KP + k - 1];
-            if (__ballot((ok0 && better(v0, i0, tv, ti)) || (ok1 && better(v1, i1, tv, ti))) == 0ull) continue;
-            TopList<KP> L;
-#pragma unroll
-            for (int s = 0; s < KP / 64; ++s) { L.v[s] = Lv[q * KP + s * 64 + lane]; L.i[s] = Li[q * KP + s * 64 + lane]; }
-            fold<KP>(L, v0, i0, ok0, k, lane);
-            fold<KP>(L, v1, i1, ok1, k, lane);
-#pragma unroll
-            for (int s = 0; s < KP / 64; ++s) { Lv[q * KP + s * 64 + lane] = L.v[s]; Li[q * KP + s * 64 + lane] = L.i[s]; }
-        }
+        topk_lds_scan<QT, KP, SimDescending>(Lv, Li, k, q0, a.Nq, lane, w, [&](int q, int h) {
+            return TopCand{St[q * SP + 64 * h + lane], h ? i1 : i0, h ? ok1 : ok0};
+        });
     }
 
-    // a wave's 16 lists are its own: no barrier between its last scan and this
-    float* ov = a.out_v + (long)blockIdx.y * a.split_stride;
-    int* oi = a.out_i + (long)blockIdx.y * a.split_stride;
-    for (int qq = 0; qq < QT / 4; ++qq) {
-        const int q = w * (QT / 4) + qq;
-        const long gq = q0 + q;
-        if (gq >= a.Nq) break;
-        for (int j = lane; j < k; j += 64) {
-            ov[gq * k + j] = Lv[q * KP + j];
-            oi[gq * k + j] = Li[q * KP + j];
-        }
-    }
-}
-
-// one wave per query: the splits' lists [splits][Nq][k] -> the k best.  Slots a split could not fill carry INT_MAX.
-template <int KP>
-__global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ wv, const int* __restrict__ wi, int splits,
-                                                        long split_stride, int Nq, int k, float* __restrict__ top_sim,
-                                                        int* __restrict__ top_idx) {
-    const int lane = threadIdx.x & 63;
-    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= Nq) return;                                             // whole waves leave; no barrier below
-    TopList<KP> L;
-    L.clear();
-    for (int s = 0; s < splits; ++s) {
-        const long base = (long)s * split_stride + q * k;
-        for (int j0 = 0; j0 < k; j0 += 64) {
-            const int j = j0 + lane;
-            const bool in = j < k;
-            const float cv = in ? wv[base + j] : 0.f;
-            const int ci = in ? wi[base + j] : INT_MAX;
-            fold<KP>(L, cv, ci, in && ci != INT_MAX, k, lane);
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < KP / 64; ++s) {
-        const int j = s * 64 + lane;
-        if (j < k) { top_sim[q * k + j] = L.v[s]; top_idx[q * k + j] = L.i[s]; }
-    }
+    topk_lds_write<QT, KP>(Lv, Li, k, q0, a.Nq, lane, w, a.out_v + (long)blockIdx.y * a.split_stride,
+                           a.out_i + (long)blockIdx.y * a.split_stride);
 }
 
 // Weighted vote, one wave per query.  Neighbour j (lanes hold j = lane and lane + 64) weighs exp((s_j - max_j s) inv_t); a
@@ -295,26 +188,29 @@ struct KnnPlan {
     long ws_bytes;
 };
 
-// Splits: enough workgroups to fill the chip when there are few query tiles, at least four bank tiles per split.  The workspace
-// figure is a bound on splits * Nq * k * 8 that grows with Nq and with k: q_tiles * splits <= min(q_tiles + TARGET_WG - 1,
-// q_tiles * max_splits) because splits <= ceil(TARGET_WG / q_tiles).
+// Splits (plan_splits): at least four bank tiles each.  The workspace figure is a bound on splits * Nq * k * 8 that grows with
+// Nq and with k: q_tiles * splits <= min(q_tiles + TARGET_WG - 1, q_tiles * max_splits) because splits <= ceil(TARGET_WG /
+// q_tiles).
 bool knn_plan(int Nq, long Nb, int k, KnnPlan& p) {
     if (!(k >= 1 && k <= 128 && (long)k <= Nb && Nb < (1L << 31) && Nq >= 1)) return false;
     p.q_tiles = ((long)Nq + QT - 1) / QT;
     p.bank_tiles = (int)((Nb + BT - 1) / BT);
-    const long max_splits = p.bank_tiles / 4 > 0 ? p.bank_tiles / 4 : 1;
-    long splits = (TARGET_WG + p.q_tiles - 1) / p.q_tiles;
-    if (splits > max_splits) splits = max_splits;
-    p.tiles_per_split = (int)((p.bank_tiles + splits - 1) / splits);
-    p.splits = (p.bank_tiles + p.tiles_per_split - 1) / p.tiles_per_split;       // no empty split
-    const long a = p.q_tiles + TARGET_WG - 1, b = p.q_tiles * max_splits;
+    const SplitPlan sp = plan_splits(p.q_tiles, p.bank_tiles, 4);
+    p.splits = sp.splits;
+    p.tiles_per_split = sp.tiles_per_split;
+    const long a = p.q_tiles + TARGET_WG - 1, b = p.q_tiles * sp.max_splits;
     p.ws_bytes = (a < b ? a : b) * QT * (long)k * 8;
     return true;
 }
 
-template <typename K>
-bool allow_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+template <int KP>
+int knn_launch(const KnnArgs& a, const KnnPlan& p, float* wv, int* wi, float* top_sim, int* top_idx, hipStream_t s) {
+    if (!allow_dynamic_lds<knn_topk_kernel<KP>>(knn_lds_bytes(KP))) return ASSL_ELAUNCH;
+    hipLaunchKernelGGL(knn_topk_kernel<KP>, dim3((unsigned)p.q_tiles, (unsigned)p.splits), dim3(256), knn_lds_bytes(KP), s, a);
+    if (p.splits > 1)
+        hipLaunchKernelGGL((topk_merge_kernel<KP, SimDescending>), dim3((unsigned)(((long)a.Nq + 3) / 4)), dim3(256), 0, s, wv, wi,
+                           p.splits, a.split_stride, a.Nq, a.k, top_sim, top_idx);
+    ASSL_LAUNCH_CHECK();
 }
 
 }  // namespace
@@ -346,22 +242,7 @@ extern "C" int audiossl_knn_topk(const void* q, const void* bank, int Nq, long N
     int* wi = reinterpret_cast<int*>(wv + (long)p.splits * a.split_stride);
     a.out_v = p.splits == 1 ? top_sim : wv;
     a.out_i = p.splits == 1 ? top_idx : wi;
-    const dim3 grid((unsigned)p.q_tiles, (unsigned)p.splits);
-    const unsigned mgrid = (unsigned)(((long)Nq + 3) / 4);
-    if (k <= 64) {
-        static bool attr_set = false;
-        if (!attr_set) { if (!allow_lds(knn_topk_kernel<64>, knn_lds_bytes(64))) return ASSL_ELAUNCH; attr_set = true; }
-        hipLaunchKernelGGL(knn_topk_kernel<64>, grid, dim3(256), knn_lds_bytes(64), s, a);
-        if (p.splits > 1)
-            hipLaunchKernelGGL(knn_merge_kernel<64>, dim3(mgrid), dim3(256), 0, s, wv, wi, p.splits, a.split_stride, Nq, k, top_sim, top_idx);
-    } else {
-        static bool attr_set = false;
-        if (!attr_set) { if (!allow_lds(knn_topk_kernel<128>, knn_lds_bytes(128))) return ASSL_ELAUNCH; attr_set = true; }
-        hipLaunchKernelGGL(knn_topk_kernel<128>, grid, dim3(256), knn_lds_bytes(128), s, a);
-        if (p.splits > 1)
-            hipLaunchKernelGGL(knn_merge_kernel<128>, dim3(mgrid), dim3(256), 0, s, wv, wi, p.splits, a.split_stride, Nq, k, top_sim, top_idx);
-    }
-    ASSL_LAUNCH_CHECK();
+    return k <= 64 ? knn_launch<64>(a, p, wv, wi, top_sim, top_idx, s) : knn_launch<128>(a, p, wv, wi, top_sim, top_idx, s);
 }
 
 extern "C" int audiossl_knn_vote(const float* top_sim, const int* top_idx, const long long* bank_label, int Nq, int k, long Nb,

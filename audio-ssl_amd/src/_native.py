@@ -156,5 +156,12 @@ def call_host(name, *args):
         raise RuntimeError(f"{full} failed: {ERRORS.get(rc, rc)}")
 
 
+def workspace_bytes(name, *ints):
+    """Bytes of workspace that `audiossl_<name>(*ints, long* bytes)` asks for."""
+    b = ctypes.c_long(0)
+    call_host(name, *(int(i) for i in ints), ctypes.addressof(b))
+    return int(b.value)
+
+
 def torch_dtype(dtype):
     return torch.float32 if dtype == F32 else torch.bfloat16

@@ -15,7 +15,6 @@ so no n x n matrix is ever stored.  The median is an exact order statistic of th
 linear Gram nor any distance, and it removes the cancellation an offset would bring into both.
 Everything allocates through torch; the only host synchronisation is reading the 8 result values.  Single GPU.
 """
-import ctypes
 
 import torch
 import torch.nn.functional as F
@@ -29,9 +28,7 @@ TERMS = ("cka", "hsic_xy", "hsic_xx", "hsic_yy", "s_kl", "s_kk", "s_ll")
 
 
 def workspace_bytes(n, p, q):
-    b = ctypes.c_long(0)
-    N.call_host("cka_workspace", int(n), int(p), int(q), ctypes.addressof(b))
-    return int(b.value)
+    return N.workspace_bytes("cka_workspace", n, p, q)
 
 
 def _prepare(x, center):

@@ -7,7 +7,6 @@ between the 5th and 6th neighbour is around 1e-4 of the squared norm - below bf1
 fp32 end to end (fp32-input MFMA, the n x n matrix never stored) and orders candidates by (d2 ascending, row ascending).
 Everything allocates through torch; single GPU.
 """
-import ctypes
 import math
 from collections import namedtuple
 
@@ -23,15 +22,11 @@ Csr = namedtuple("Csr", "rowptr col w nnz n")
 
 
 def graph_workspace_bytes(n, k):
-    b = ctypes.c_long(0)
-    N.call_host("knn_graph_workspace", int(n), int(k), ctypes.addressof(b))
-    return int(b.value)
+    return N.workspace_bytes("knn_graph_workspace", n, k)
 
 
 def pic_workspace_bytes(n, k):
-    b = ctypes.c_long(0)
-    N.call_host("pic_workspace", int(n), int(k), ctypes.addressof(b))
-    return int(b.value)
+    return N.workspace_bytes("pic_workspace", n, k)
 
 
 def knn_graph(x, k):

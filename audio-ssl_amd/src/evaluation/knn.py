@@ -7,7 +7,6 @@ kernel, so the [Nq, Nb] similarity matrix is never stored; `audiossl_knn_vote` t
 Everything here allocates through torch (outputs, the kernel's workspace, the normalised bf16 copies), so torch's memory
 statistics see every byte.  Single GPU: the bank lives on one device (sharding it over ranks is out of scope).
 """
-import ctypes
 
 import torch
 
@@ -39,9 +38,7 @@ def normalize_bf16(x):
 
 
 def workspace_bytes(nq, nb, k):
-    b = ctypes.c_long(0)
-    N.call_host("knn_workspace", int(nq), int(nb), int(k), ctypes.addressof(b))
-    return int(b.value)
+    return N.workspace_bytes("knn_workspace", nq, nb, k)
 
 
 def knn_topk_bf16(q, bank, k):

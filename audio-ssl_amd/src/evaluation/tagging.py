@@ -12,7 +12,6 @@ integer pair counts of each class's positives (no sort; csrc/tagging.hip) and on
 allocates through torch (outputs and the kernel's workspace), so torch's memory statistics see every byte.  Single GPU.
 """
 import csv
-import ctypes
 import math
 import statistics
 
@@ -99,9 +98,7 @@ def bce_with_logits(logits, targets):
 
 # --------------------------------------------------------------------------------------------------------------- metrics
 def workspace_bytes(n, c):
-    b = ctypes.c_long(0)
-    N.call_host("tagging_workspace", int(n), int(c), ctypes.addressof(b))
-    return int(b.value)
+    return N.workspace_bytes("tagging_workspace", n, c)
 
 
 def tagging_counts(scores, targets):

@@ -48,7 +48,10 @@ def _ints(shape, seed):
 
 # ---- 1. exact cases, ties included -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nq,nb,d,k", [(1, 128, 32, 128), (63, 1000, 256, 128), (130, 70001, 64, 20), (64, 4096, 2048, 1),
-                                       (5, 20, 96, 20)])
+                                       (5, 20, 96, 20),
+                                       (70, 1100, 32, 64),     # one-slot list, every lane in use; 2 splits: the merge runs
+                                       (70, 1100, 32, 65),     # two-slot list, k-th entry = lane 0 of slot 1: every insertion carries
+                                       (3, 130, 32, 65)])      # two-slot list, one split, second bank tile with 2 valid rows
 def test_topk_exact_on_integer_inputs_ties_by_ascending_row(nq, nb, d, k):
     """Entries in -2..2 are exact in bf16 and every dot product is an integer below 2^24: exact in fp32 in any summation order.
     About 110-160 distinct values per row, so at Nb = 70,001 almost every returned position sits inside a tie: this pins the
