@@ -1,5 +1,6 @@
-"""Exact nearest-neighbour graphs and the graph stages of power-iteration clustering (csrc/graph.hip), plus the partition
-score the reference's DeepCluster trainers use to compare successive labelings.
+"""Exact nearest-neighbour graphs and the graph stages of power-iteration clustering (csrc/graph.hip), the partition score the
+reference's DeepCluster trainers use to compare successive labelings, and the silhouette coefficient of one labeling on the
+features it was computed on (csrc/silhouette.hip).
 
 `knn_graph` is NOT `knn_topk`: that one forms cosine similarities on the bf16 MFMA pipe, which suits a vote over 20 neighbours
 at temperature 0.07.  A graph is a discrete input to everything after it, and on whitened, L2-normalised features the gap
@@ -27,6 +28,10 @@ def graph_workspace_bytes(n, k):
 
 def pic_workspace_bytes(n, k):
     return N.workspace_bytes("pic_workspace", n, k)
+
+
+def silhouette_workspace_bytes(n):
+    return N.workspace_bytes("silhouette_workspace", n)
 
 
 def knn_graph(x, k):
@@ -131,3 +136,48 @@ def partition_nmi(a, b):
     denom = 0.5 * (ha + hb)
     eps = torch.finfo(torch.float64).eps
     return float(mi / denom.clamp_min(eps))
+
+
+@torch.no_grad()
+def silhouette_samples(x, labels):
+    """sklearn's `silhouette_samples(x, labels)` (Euclidean) -> fp64 [n] on x's device, in the caller's order: s_i = (b_i - a_i) /
+    max(a_i, b_i) with a_i the mean distance to the other members of i's cluster and b_i the smallest mean distance to another
+    cluster's members; 0 for a one-member cluster.  x [n, d] (device); labels: any integer sequence / array / tensor, values are
+    arbitrary (negative, sparse).  No distance matrix is stored: the rows are sorted by cluster (stable) and `audiossl_silhouette`
+    walks all pairs once.  d is zero-padded to a multiple of 4.  Reads the cluster sizes back (one small copy to the host)."""
+    if not x.is_cuda:
+        raise RuntimeError("audiossl HIP kernels need device tensors (no CPU fallback exists)")
+    if x.dim() != 2:
+        raise ValueError(f"points are [n, d], got {tuple(x.shape)}")
+    n, d = x.shape
+    labels = torch.as_tensor(labels).reshape(-1)
+    if labels.numel() != n:
+        raise ValueError(f"{n} points and {labels.numel()} labels")
+    if labels.is_floating_point() or labels.is_complex():
+        raise ValueError(f"labels are integers, got {labels.dtype}")
+    if not 1 <= d <= MAX_WIDTH:
+        raise ValueError(f"width must be in [1, {MAX_WIDTH}], got {d}")
+    _, inverse, counts = torch.unique(labels.to(x.device), return_inverse=True, return_counts=True)
+    K = counts.numel()
+    if not 2 <= K <= n - 1:
+        raise ValueError(f"Number of labels is {K}. Valid values are 2 to n_samples - 1 (inclusive)")      # sklearn's rule and wording
+    order = torch.sort(inverse, stable=True).indices
+    xs = x.float()[order]
+    if d % 4:
+        xs = F.pad(xs, (0, 4 - d % 4))
+    xs = xs.contiguous()
+    seg = torch.zeros(K + 1, dtype=torch.int32, device=x.device)
+    seg[1:] = torch.cumsum(counts, 0)
+    seg_host = seg.cpu()                                                     # the entry point checks it before any launch
+    s = torch.empty(n, dtype=torch.float64, device=x.device)
+    nbytes = silhouette_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    N.call("silhouette", xs, n, xs.shape[1], seg, seg_host.data_ptr(), K, s, ws, nbytes)
+    out = torch.empty_like(s)
+    out[order] = s
+    return out
+
+
+def silhouette_score(x, labels):
+    """sklearn's `silhouette_score(x, labels)`: the fp64 mean of `silhouette_samples` -> python float."""
+    return float(silhouette_samples(x, labels).mean())

@@ -96,6 +96,7 @@ class Kmeans(object):
     def cluster(self, data, verbose=False, pca=128):
         end = time.time()
         xb = preprocess_features(data, pca=pca)
+        self.features = xb                                          # what was clustered: `silhouette_score(self.features, labels)`
         I, loss = run_kmeans(xb, self.k, verbose)
         self.images_lists = [[] for _ in range(self.k)]
         for i in range(len(data)):
@@ -204,6 +205,7 @@ class PIC(object):
     def cluster(self, data, verbose=False, pca=128):
         end = time.time()
         xb = preprocess_features(data, pca=pca)
+        self.features = xb
         I, D = make_graph(xb, self.nnn)
         clust = np.asarray(run_pic(I, D, self.sigma, self.alpha), dtype=np.int64)
         if self.distribute_singletons:

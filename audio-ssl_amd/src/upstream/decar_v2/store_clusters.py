@@ -5,23 +5,69 @@ PCA-whiten, cluster, and write the `files,label` CSV `train_upstream.py --upstre
     python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv --k 585 \
         --out labelled.csv
     python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv \
-        --clustering pic --out labelled.csv
+        --clustering pic --score --out labelled.csv
+    python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv \
+        --k_sweep 64,128,256 --out labelled.csv
 
 `--clustering kmeans` (the default) needs `--k`.  `--clustering pic` is the reference's other algorithm (`PIC`, imported next to
 `Kmeans` at `store_clusters.py:18`): power-iteration clustering on an exact nearest-neighbour graph, which finds the number of
 clusters itself; the summary line prints that number, which is what `pretrain.task_label` has to be set to.
 `--compare other.csv` prints the normalised mutual information between the labels just written and those of another
 `files,label` file over the same files (a k-means labeling against a PIC one, or pseudo-labels against real ones).
+`--score` prints the silhouette coefficient (sklearn's `silhouette_score`, Euclidean) of the labels just written on the whitened
+features they were computed on: the label-free answer to "is this labeling any good" (`src.evaluation.graph.silhouette_score`,
+all pairs on the GPU, no distance matrix stored).  `--k_sweep 64,128,256` takes the place of `--k`: the files are embedded and
+whitened once, k-means runs for every k in the order given, one line per k reports its silhouette, and the labeling with the
+highest silhouette (a tie: the smaller k) is written; the reference has neither.
 `--window random` is the default: the reference draws `extract_window` for every clip.  Single GPU.
 """
 import argparse
 import sys
 
+import numpy as np
 import pandas as pd
 import torch
 import yaml
 
-from src.upstream.decar_v2.clustering import PIC, Kmeans, write_pseudolabel_csv
+from src.upstream.decar_v2.clustering import PIC, Kmeans, preprocess_features, run_kmeans, write_pseudolabel_csv
+
+
+def _silhouette(features, labels):
+    """-> (score or None when the labeling has fewer than 2 or more than n - 1 clusters, clusters, one-member clusters)"""
+    from src.evaluation.graph import silhouette_score
+    sizes = np.unique(np.asarray(labels), return_counts=True)[1]
+    ok = 2 <= len(sizes) <= len(labels) - 1
+    return (silhouette_score(features, labels) if ok else None), len(sizes), int((sizes == 1).sum())
+
+
+def _fmt(score):
+    return "n/a" if score is None else f"{score:.6f}"
+
+
+def sweep_kmeans(feats, ks, pca, verbose=False):
+    """k-means for every k of `ks` on the same whitened features -> the `Kmeans` of the k with the highest silhouette (a tie: the
+    smaller k), its loss and its silhouette; one table line per k.  The seeds are the draws successive `Kmeans(k).cluster` calls
+    would make."""
+    xb = preprocess_features(feats, pca=pca)
+    n = xb.shape[0]
+    if max(ks) > n:
+        raise ValueError(f"--k_sweep: k = {max(ks)} exceeds the {n} files")
+    best = None
+    for k in ks:
+        I, loss = run_kmeans(xb, k, verbose)
+        score, used, _ = _silhouette(xb, I)
+        print(f"k {k}: {used} non-empty clusters, k-means loss {loss:.6g}, silhouette {_fmt(score)}")
+        if score is not None and (best is None or score > best[0] or (score == best[0] and k < best[1])):
+            best = (score, k, I, loss)
+    if best is None:
+        raise ValueError("--k_sweep: no k gave a labeling with 2 .. n - 1 non-empty clusters, nothing to choose from")
+    score, k, I, loss = best
+    model = Kmeans(k)
+    model.features = xb
+    model.images_lists = [[] for _ in range(k)]
+    for i, c in enumerate(I):
+        model.images_lists[c].append(i)
+    return model, loss, score
 
 
 def main(args):
@@ -37,6 +83,7 @@ def main(args):
     duration = float(embedder.model.config["pretrain"]["input"]["length_wave"])
     feats = extract_embeddings(embedder, files, batch_size=args.batch_size, window=args.window, duration=duration)
     pca = min(args.pca, feats.shape[1], max(1, len(files) - 1))                                  # rank of the covariance
+    chosen = None
     if args.clustering == "pic":
         if args.k is not None:
             print("warning: --k is ignored with --clustering pic (the number of clusters is found)", file=sys.stderr)
@@ -45,10 +92,16 @@ def main(args):
         labels = write_pseudolabel_csv(files, model, args.out, header="files,label")
         print(f"{len(files)} files, {len(model.images_lists)} clusters, pic sigma {args.sigma:g} nnn {args.nnn} -> {args.out}")
     else:
-        model = Kmeans(args.k)
-        loss = model.cluster(feats, verbose=args.verbose, pca=pca)
+        if args.k_sweep:
+            model, loss, chosen = sweep_kmeans(feats, args.k_sweep, pca, verbose=args.verbose)
+        else:
+            model = Kmeans(args.k)
+            loss = model.cluster(feats, verbose=args.verbose, pca=pca)
         labels = write_pseudolabel_csv(files, model, args.out, header="files,label")
-        print(f"{len(files)} files, {args.k} clusters, k-means loss {loss:.6g} -> {args.out}")
+        print(f"{len(files)} files, {model.k} clusters, k-means loss {loss:.6g} -> {args.out}")
+    if args.score:
+        score, count, singles = _silhouette(model.features, labels)
+        print(f"silhouette {_fmt(score)} ({count} clusters, {singles} singletons)")
     if args.compare:
         from src.evaluation.graph import partition_nmi
         other = pd.read_csv(args.compare)
@@ -56,7 +109,19 @@ def main(args):
             raise ValueError(f"{args.compare} does not list the files of {args.input} in the same order")
         codes = pd.factorize(other["label"])[0]
         print(f"NMI against {args.compare}: {partition_nmi(labels, codes):.6f}")
+    if chosen is not None:
+        print(f"chosen k {model.k} of {','.join(str(k) for k in args.k_sweep)} (silhouette {chosen:.6f})")
     return labels
+
+
+def _k_list(text):
+    try:
+        ks = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a comma-separated list of integers, got {text!r}")
+    if not ks or min(ks) < 1:
+        raise argparse.ArgumentTypeError(f"every k must be at least 1, got {text!r}")
+    return ks
 
 
 def get_args(argv=None):
@@ -66,6 +131,8 @@ def get_args(argv=None):
     parser.add_argument("--input", type=str, required=True, help="csv with a `files` column")
     parser.add_argument("--clustering", choices=("kmeans", "pic"), default="kmeans")
     parser.add_argument("--k", type=int, default=None, help="number of clusters for k-means (the reference uses 585); ignored by pic")
+    parser.add_argument("--k_sweep", type=_k_list, default=None,
+                        help="k-means: comma-separated k values in place of --k; the k with the highest silhouette is written")
     parser.add_argument("--out", type=str, required=True, help="`files,label` csv to write")
     parser.add_argument("--pca", type=int, default=128)
     parser.add_argument("--sigma", type=float, default=0.2, help="pic: bandwidth of the Gaussian kernel")
@@ -73,13 +140,18 @@ def get_args(argv=None):
     parser.add_argument("--alpha", type=float, default=0.001, help="pic: damping of the power iteration")
     parser.add_argument("--no_distribute_singletons", action="store_true", help="pic: keep one-member clusters")
     parser.add_argument("--compare", type=str, default=None, help="another `files,label` csv: print the NMI against it")
+    parser.add_argument("--score", action="store_true", help="print the silhouette coefficient of the labels just written")
     parser.add_argument("--window", choices=("center", "random"), default="random")
     parser.add_argument("--layer", choices=("backbone", "head"), default="backbone")
     parser.add_argument("--batch_size", type=int, default=64)
     parser.add_argument("-c", "--config", metavar="CONFIG_PATH", default=None)
     parser.add_argument("--verbose", action="store_true")
     args = parser.parse_args(argv)
-    if args.clustering == "kmeans" and args.k is None:
+    if args.k_sweep is not None and args.k is not None:
+        parser.error("--k_sweep takes the place of --k: give one of them")
+    if args.k_sweep is not None and args.clustering == "pic":
+        parser.error("--k_sweep is for k-means: pic finds the number of clusters itself")
+    if args.clustering == "kmeans" and args.k is None and args.k_sweep is None:
         parser.error("the following arguments are required: --k")       # argparse's own wording for a required option
     return args
 

@@ -545,6 +545,24 @@ int audiossl_pic_power(const int* rowptr, const int* col, const double* w, int n
 int audiossl_pic_assign(const int* rowptr, const int* col, const double* w, const double* v, int n, long cap, int* label,
                         int* count, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- silhouette coefficient of a labeling on its features (csrc/silhouette.hip): sklearn's `silhouette_samples`, Euclidean -------
+ * The label-free score of a pseudo-labeling (`store_clusters --score`, `--k_sweep`); the reference has no counterpart.
+ * silhouette: xs [n][d] row-major fp32, rows SORTED BY CLUSTER; seg [K + 1] int32 offsets (device): cluster c is rows seg[c] ..
+ *   seg[c + 1] - 1; seg_host = the caller's host copy of seg, checked before any launch.  s [n] fp64, in the sorted order:
+ *     a_i = mean distance to the other members of i's cluster, b_i = min over the other clusters of the mean distance to their
+ *     members, s_i = (b_i - a_i) / max(a_i, b_i); s_i = 0 when i's cluster has one member and for 0 / 0.
+ *   dist_ij = sqrt(max(0, (n_i + n_j) - 2 g_ij)): g_ij and n_i = g_ii by knn_graph_l2's chain (fp32-input MFMA, d in index order),
+ *   so a repeated row is at distance exactly 0; (i, i) leaves by index; the fp32 sqrt is correctly rounded; every sum of
+ *   distances, the means, the min and the quotient are fp64.  Neither the n x n matrix nor an n x K table is stored: one
+ *   workgroup per 64 rows walks all columns and folds a cluster's sum when its last column has passed.  No atomics; the workspace
+ *   (n norms) needs no clearing; two calls agree bit for bit; nothing synchronises with the host.
+ *   n >= 3, d % 4 == 0 (pad with zero columns), 4 <= d <= 4096, 2 <= K <= n - 1, seg_host[0] == 0, seg_host[K] == n, every
+ *   segment non-empty (EINVAL); xs and workspace 16-byte aligned (EALIGN); inputs finite.
+ * silhouette_workspace (host): bytes for silhouette, non-decreasing in n. */
+int audiossl_silhouette_workspace(int n, long* bytes);
+int audiossl_silhouette(const float* xs, int n, int d, const int* seg, const int* seg_host, int K, double* s, void* workspace,
+                        long workspace_bytes, void* stream);
+
 /* ---- K22 audio tagging (multi-label downstream, csrc/tagging.hip): nn.BCEWithLogitsLoss (the "bce_logit" of
  * `extras/mast_new/mast/mvit/models/losses.py:38`) on the multi-hot / mixed targets of `mast/dataloader.py:157-184` and the per-class metrics of
  * `extras/mast_new/mast/utilities/stats.py:11-57` (sklearn's average_precision_score / roc_auc_score, class by class on the host
