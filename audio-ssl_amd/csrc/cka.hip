@@ -7,16 +7,12 @@
 // CKA = HSIC_xy / sqrt(HSIC_xx HSIC_yy) follow.  Subtracting the column means of X and Y first (cka_center; the Python layer
 // does it by default) changes neither the centred linear Gram nor any distance and removes the cancellation in both.
 //
-// Tile.  g_ij = <x_i, x_j> on the fp32-input MFMA (mfma_f32_32x32x2f32: exact f32, a k-ordered fmaf chain).  A workgroup
-// (4 waves) owns 64 rows i and walks 128-column tiles j; features are staged through LDS in chunks of 32 (the next chunk's
-// global loads in flight during the MFMAs).  The Gram tile is TRANSPOSED as in knn.hip: A = the walked rows j, B = the owned
-// rows i, so a lane's MFMA column is one owned row and its 2 x 16 registers are 32 + 32 columns j - row sums never leave the
-// lane.  Wave w: owned rows 32 (w & 1) .., walked columns 64 (w >> 1) ..: two independent accumulators per wave (the
-// dependent latency of the instruction is its issue interval: two chains per wave and two workgroups per CU keep the pipe
-// busy).  A lane half h reads the float4 at k = 8 g + 4 h of its row and feeds element s to step s, so one MFMA sums
-// k = 8 g + s (h = 0) then 8 g + 4 + s (h = 1): the chain order is 0 4 1 5 2 6 3 7 inside every group of 8.  cka_norm_kernel
-// runs the same chain for g_ii, so (g_ii + g_jj) - 2 g_ij is 0 wherever row j repeats row i, and i == j is set to 0 outright.
-// Rows and columns past n and features past p are staged as zeros and masked out of every sum and histogram.
+// Tile.  g_ij = <x_i, x_j> is the fp32 Gram tile of gram_tile.h in halves chain order (0 4 1 5 2 6 3 7 inside every group
+// of 8), g_ii its norm kernel, so (g_ii + g_jj) - 2 g_ij is 0 wherever row j repeats row i, and i == j is set to 0
+// outright.  The tile stays in registers here: a lane's MFMA column is one owned row and its 2 x 16 registers are 32 + 32
+// columns j, so row sums never leave the lane; the sweep calls the tile twice per column tile (x, then y) and two
+// workgroups per CU keep the pipe busy.  Rows and columns past n are masked out of every sum and histogram.  What this
+// file adds on top of the tile: the HSIC sums, the histogram passes of the median rule, the select and the finalise.
 //
 // RBF.  d_ij = max((g_ii + g_jj) - 2 g_ij, 0), K_ij = exp(d_ij c), c = (float)(-0.5 / sigma^2) formed in fp64 and rounded once.
 // sigma^2 = median of the non-zero d_ij (the reference's np.median(KX[KX != 0]); the matrix is symmetric, so the median over
@@ -32,17 +28,13 @@
 // runs agree bit for bit.  The kernels initialise whatever they read; the workspace needs no clearing by the caller.
 // The full square is swept (K and L are symmetric; the triangle would halve a cost of milliseconds).
 #include "topk.h"          // plan_splits, TARGET_WG
+#include "gram_tile.h"
 
 namespace {
 
-constexpr int RT = 64;               // owned rows per workgroup
-constexpr int CT = 128;              // walked columns per tile
-constexpr int KC = 32;               // feature chunk per staging step
-constexpr int RP = KC + 4;           // staging pitch (floats): 144-byte rows, 16-byte aligned float4 fragments
 constexpr int MIN_TILES = 2;         // column tiles per split at least
 constexpr int NBIN = 2048;           // radix-select bins per pass (11 + 11 + 10 bits)
 constexpr int MAX_N = 65536;
-constexpr int MAX_P = 4096;
 
 enum { MODE_LINEAR = 0, MODE_RBF = 1, MODE_HIST = 2 };
 
@@ -60,9 +52,9 @@ struct CkaPlan {
 // row_blocks * splits, so it grows with n.
 bool cka_plan(long n, CkaPlan& p) {
     if (!(n >= 2 && n <= MAX_N)) return false;
-    p.row_blocks = (int)((n + RT - 1) / RT);
-    p.col_tiles = (int)((n + CT - 1) / CT);
-    p.n_pad = (long)p.row_blocks * RT;
+    p.row_blocks = (int)((n + QT - 1) / QT);
+    p.col_tiles = (int)((n + BT - 1) / BT);
+    p.n_pad = (long)p.row_blocks * QT;
     const SplitPlan sp = plan_splits(p.row_blocks, p.col_tiles, MIN_TILES);
     p.splits = sp.splits;
     p.tiles_per_split = sp.tiles_per_split;
@@ -70,8 +62,8 @@ bool cka_plan(long n, CkaPlan& p) {
     long o = 0;
     p.off_gx = o;    o += p.n_pad * 4;
     p.off_gy = o;    o += p.n_pad * 4;
-    p.off_rk = o;    o += wg_bound * RT * 8;
-    p.off_rl = o;    o += wg_bound * RT * 8;
+    p.off_rk = o;    o += wg_bound * QT * 8;
+    p.off_rl = o;    o += wg_bound * QT * 8;
     p.off_s = o;     o += wg_bound * 4 * 8;
     p.off_hist = o;  o += 2L * NBIN * 8;
     p.off_state = o; o += ST_WORDS * 8;
@@ -98,84 +90,14 @@ struct CkaArgs {
     int dshift, dmask, pshift;    // HIST: digit = (bits >> dshift) & dmask, followed iff (bits >> pshift) == prefix
 };
 
-// g_ii with the Gram tile's own fmaf chain: k order 0 4 1 5 2 6 3 7 inside every group of 8, zero past p.
-__global__ __launch_bounds__(256) void cka_norm_kernel(const float* __restrict__ x, int n, int p, long n_pad, float* __restrict__ g) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pad) return;
-    float acc = 0.f;
-    if (i < n) {
-        const float* r = x + i * p;
-        for (int k0 = 0; k0 < p; k0 += 8) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(r + k0);
-            const f32x4 b = (k0 + 4 < p) ? *reinterpret_cast<const f32x4*>(r + k0 + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                acc = __builtin_fmaf(a[s], a[s], acc);
-                acc = __builtin_fmaf(b[s], b[s], acc);
-            }
-        }
-    }
-    g[i] = acc;
-}
-
-// One 128 (walked j) x 64 (owned i) Gram tile of the [n][P] matrix m; this wave's 64 x 32 part in acc[0..1].
-// Every thread of the workgroup calls it (barriers inside).
-__device__ __forceinline__ void gram_tile(const float* __restrict__ m, int n, int P, long r0, long c0, float* Os, float* Ws,
-                                          f32x16 (&acc)[2]) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, half = lane >> 5, l31 = lane & 31;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    // staging: 8 threads per row (16 bytes each), rows tid / 8 + 32 v
-    const int srow = tid >> 3, scol = (tid & 7) * 4;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 ro[2], rw[4];
-    auto load_chunk = [&](int c) {
-        const int col = c * KC + scol;
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const long gr = r0 + srow + 32 * v;
-            ro[v] = (gr < n && col < P) ? *reinterpret_cast<const f32x4*>(m + gr * P + col) : zero4;
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const long gc = c0 + srow + 32 * v;
-            rw[v] = (gc < n && col < P) ? *reinterpret_cast<const f32x4*>(m + gc * P + col) : zero4;
-        }
-    };
-    const int nchunk = (P + KC - 1) / KC;
-    load_chunk(0);
-    for (int c = 0; c < nchunk; ++c) {
-        __syncthreads();                                             // the previous chunk's fragment reads are done
-#pragma unroll
-        for (int v = 0; v < 2; ++v) *reinterpret_cast<f32x4*>(Os + (srow + 32 * v) * RP + scol) = ro[v];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) *reinterpret_cast<f32x4*>(Ws + (srow + 32 * v) * RP + scol) = rw[v];
-        __syncthreads();
-        if (c + 1 < nchunk) load_chunk(c + 1);
-#pragma unroll
-        for (int g = 0; g < KC / 8; ++g) {
-            const f32x4 fo = *reinterpret_cast<const f32x4*>(Os + ((w & 1) * 32 + l31) * RP + g * 8 + 4 * half);
-            const f32x4 f0 = *reinterpret_cast<const f32x4*>(Ws + ((w >> 1) * 64 + l31) * RP + g * 8 + 4 * half);
-            const f32x4 f1 = *reinterpret_cast<const f32x4*>(Ws + ((w >> 1) * 64 + 32 + l31) * RP + g * 8 + 4 * half);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f0[s], fo[s], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f1[s], fo[s], acc[1], 0, 0, 0);
-            }
-        }
-    }
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void cka_sweep_kernel(CkaArgs a) {
-    __shared__ __attribute__((aligned(16))) float Os[RT * RP];
-    __shared__ __attribute__((aligned(16))) float Ws[CT * RP];
+    __shared__ __attribute__((aligned(16))) float Os[QT * RP];
+    __shared__ __attribute__((aligned(16))) float Ws[BT * RP];
     __shared__ unsigned int hist_s[MODE == MODE_HIST ? 2 * NBIN : 1];
     __shared__ double red[MODE == MODE_HIST ? 1 : 4 * 64 * 2 + 16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const long r0 = (long)blockIdx.x * RT;
+    const long r0 = (long)blockIdx.x * QT;
     const int n = a.n;
     const long gi = r0 + (w & 1) * 32 + l31;                         // this lane's owned row
     const bool row_ok = gi < n;
@@ -201,12 +123,12 @@ __global__ __launch_bounds__(256, 2) void cka_sweep_kernel(CkaArgs a) {
 
     double s_kl = 0., s_kk = 0., s_ll = 0., rk = 0., rl = 0.;
     for (int t = t0; t < t1; ++t) {
-        const long c0 = (long)t * CT;
-        if (MODE == MODE_HIST && c0 + CT - 1 <= r0) continue;        // no j > i in this tile (workgroup-uniform)
+        const long c0 = (long)t * BT;
+        if (MODE == MODE_HIST && c0 + BT - 1 <= r0) continue;        // no j > i in this tile (workgroup-uniform)
         f32x16 ak[2], al[2];
-        gram_tile(a.x, n, a.p, r0, c0, Os, Ws, ak);
-        if (MODE != MODE_HIST) gram_tile(a.y, n, a.q, r0, c0, Os, Ws, al);
-        // C/D map: column = lane & 31 = owned row, register r = walked column (r & 3) + 8 (r >> 2) + 4 half
+        gram_tile<ChainOrder::Halves>(a.x, n, a.p, r0, c0, Os, Ws, ak);
+        if (MODE != MODE_HIST) gram_tile<ChainOrder::Halves>(a.y, n, a.q, r0, c0, Os, Ws, al);
+        // gj: the walked column of register r (the C/D map of gram_tile.h)
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -255,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void cka_sweep_kernel(CkaArgs a) {
     rrk[w * 64 + lane] = rk;
     rrl[w * 64 + lane] = rl;
     __syncthreads();
-    if (tid < RT) {
+    if (tid < QT) {
         const int wl = tid >> 5, l = tid & 31;                       // owned row tid: waves wl and wl + 2, lanes l and l + 32
         const double k4 = ((rrk[wl * 64 + l] + rrk[wl * 64 + 32 + l]) + rrk[(wl + 2) * 64 + l]) + rrk[(wl + 2) * 64 + 32 + l];
         const double l4 = ((rrl[wl * 64 + l] + rrl[wl * 64 + 32 + l]) + rrl[(wl + 2) * 64 + l]) + rrl[(wl + 2) * 64 + 32 + l];
@@ -361,14 +283,12 @@ __global__ __launch_bounds__(256) void cka_center_kernel(const float* __restrict
         for (long i = ph; i < n; i += 8) out[i * p + col] = (float)((double)x[i * p + col] - mean);
 }
 
-bool width_ok(int p) { return p >= 4 && p <= MAX_P && p % 4 == 0; }
-
 }  // namespace
 
 extern "C" int audiossl_cka_workspace(int n, int p, int q, long* bytes) {
     CkaPlan pl;
     ASSL_REQUIRE(bytes != nullptr);
-    ASSL_REQUIRE(width_ok(p) && width_ok(q));
+    ASSL_REQUIRE(gram_width_ok(p) && gram_width_ok(q));
     ASSL_REQUIRE(cka_plan(n, pl));
     *bytes = pl.bytes;
     return ASSL_OK;
@@ -376,7 +296,7 @@ extern "C" int audiossl_cka_workspace(int n, int p, int q, long* bytes) {
 
 extern "C" int audiossl_cka_center(const float* x, int n, int p, float* out, void* stream) {
     ASSL_REQUIRE(x && out);
-    ASSL_REQUIRE(n >= 2 && n <= MAX_N && width_ok(p));
+    ASSL_REQUIRE(n >= 2 && n <= MAX_N && gram_width_ok(p));
     if (!ASSL_ALIGNED16(x) || !ASSL_ALIGNED16(out)) return ASSL_EALIGN;
     hipLaunchKernelGGL(cka_center_kernel, dim3((unsigned)((p + 31) / 32)), dim3(256), 0, S_(stream), x, n, p, out);
     ASSL_LAUNCH_CHECK();
@@ -386,7 +306,7 @@ extern "C" int audiossl_cka_sigma2(const float* x, int n, int p, double* sigma2,
                                    long workspace_bytes, void* stream) {
     CkaPlan pl;
     ASSL_REQUIRE(x && sigma2 && workspace);
-    ASSL_REQUIRE(width_ok(p));
+    ASSL_REQUIRE(gram_width_ok(p));
     ASSL_REQUIRE(cka_plan(n, pl));
     ASSL_REQUIRE(workspace_bytes >= pl.bytes);
     if (!ASSL_ALIGNED16(x) || !ASSL_ALIGNED16(workspace)) return ASSL_EALIGN;
@@ -401,7 +321,7 @@ extern "C" int audiossl_cka_sigma2(const float* x, int n, int p, double* sigma2,
     a.n = n; a.p = p; a.q = p;
     a.col_tiles = pl.col_tiles; a.tiles_per_split = pl.tiles_per_split; a.n_pad = pl.n_pad;
     ASSL_ZERO_ALWAYS(ws + pl.off_hist, (size_t)(2L * NBIN + ST_WORDS) * 8, s);      // histograms and state are adjacent
-    hipLaunchKernelGGL(cka_norm_kernel, GRID1(pl.n_pad), dim3(256), 0, s, x, n, p, pl.n_pad, reinterpret_cast<float*>(ws + pl.off_gx));
+    hipLaunchKernelGGL(gram_norm_kernel<ChainOrder::Halves>, GRID1(pl.n_pad), dim3(256), 0, s, x, n, p, pl.n_pad, reinterpret_cast<float*>(ws + pl.off_gx));
     const dim3 grid((unsigned)pl.row_blocks, (unsigned)pl.splits);
     static const int dshift[3] = {21, 10, 0}, dbits[3] = {11, 11, 10}, pshift[3] = {32, 21, 10};
     for (int pass = 0; pass < 3; ++pass) {
@@ -418,7 +338,7 @@ extern "C" int audiossl_cka_hsic(const float* x, const float* y, int n, int p, i
     CkaPlan pl;
     ASSL_REQUIRE(x && y && out && workspace);
     ASSL_REQUIRE(kernel == MODE_LINEAR || kernel == MODE_RBF);
-    ASSL_REQUIRE(width_ok(p) && width_ok(q));
+    ASSL_REQUIRE(gram_width_ok(p) && gram_width_ok(q));
     ASSL_REQUIRE(cka_plan(n, pl));
     ASSL_REQUIRE(workspace_bytes >= pl.bytes);
     if (kernel == MODE_RBF) {
@@ -440,8 +360,8 @@ extern "C" int audiossl_cka_hsic(const float* x, const float* y, int n, int p, i
     a.col_tiles = pl.col_tiles; a.tiles_per_split = pl.tiles_per_split; a.n_pad = pl.n_pad;
     const dim3 grid((unsigned)pl.row_blocks, (unsigned)pl.splits);
     if (kernel == MODE_RBF) {
-        hipLaunchKernelGGL(cka_norm_kernel, GRID1(pl.n_pad), dim3(256), 0, s, x, n, p, pl.n_pad, reinterpret_cast<float*>(ws + pl.off_gx));
-        hipLaunchKernelGGL(cka_norm_kernel, GRID1(pl.n_pad), dim3(256), 0, s, y, n, q, pl.n_pad, reinterpret_cast<float*>(ws + pl.off_gy));
+        hipLaunchKernelGGL(gram_norm_kernel<ChainOrder::Halves>, GRID1(pl.n_pad), dim3(256), 0, s, x, n, p, pl.n_pad, reinterpret_cast<float*>(ws + pl.off_gx));
+        hipLaunchKernelGGL(gram_norm_kernel<ChainOrder::Halves>, GRID1(pl.n_pad), dim3(256), 0, s, y, n, q, pl.n_pad, reinterpret_cast<float*>(ws + pl.off_gy));
         hipLaunchKernelGGL(cka_sweep_kernel<MODE_RBF>, grid, dim3(256), 0, s, a);
     } else {
         hipLaunchKernelGGL(cka_sweep_kernel<MODE_LINEAR>, grid, dim3(256), 0, s, a);

@@ -4,17 +4,12 @@
 //
 // knn_graph_l2: exact k nearest neighbours of n points among themselves, squared L2, fp32 END TO END.  The graph is a discrete
 //   input to everything after it and on whitened, normalised features the gaps between neighbours are ~1e-4 of the squared
-//   norm: far below bf16 resolution, so knn.hip's bf16 similarity does not serve.  g_ij = <x_i, x_j> on the fp32-input MFMA
-//   (mfma_f32_32x32x2f32: exact f32, a k-ordered fmaf chain) with the tile of cka.hip: a workgroup (4 waves) owns 64 rows i and
-//   walks 128-row tiles j, features staged through LDS in chunks of 32 (the next chunk's global loads in flight during the
-//   MFMAs).  The staging store interleaves every group of 8 features (even ones first), so that lane half h of MFMA step s
-//   holds feature 8 g + 2 s + h: the chain runs over d in INDEX order, graph_norm_kernel runs the same chain for n_i = g_ii,
-//   and d2_ij = max(0, (n_i + n_j) - 2 g_ij) is exactly 0 wherever row j repeats row i.  Self is excluded by INDEX, so a
-//   duplicate row is a legitimate neighbour at distance 0.
-//   The n x n matrix is never stored: the 64 x 128 tile is dumped to LDS over the dead staging buffers and wave w scans rows
-//   16w..16w+15 with the streaming selector of topk.h (k <= 64: the one-slot list), order (d2 ascending, j ascending).  Few
-//   rows: the walked rows are split over blockIdx.y, every split writes its k best to the workspace, topk_merge_kernel folds
-//   them.
+//   norm: far below bf16 resolution, so knn.hip's bf16 similarity does not serve.  g_ij = <x_i, x_j> is the fp32 Gram tile of
+//   gram_tile.h in index chain order, n_i = g_ii its norm kernel, so d2_ij = max(0, (n_i + n_j) - 2 g_ij) is exactly 0
+//   wherever row j repeats row i.  What this file adds on top of the tile: the 64 x 128 tile is dumped to LDS and wave w
+//   scans rows 16w..16w+15 with the streaming selector of topk.h (k <= 64: the one-slot list), order (d2 ascending,
+//   j ascending).  Self is excluded by INDEX, so a duplicate row is a legitimate neighbour at distance 0.  Few rows: the
+//   walked rows are split over blockIdx.y, every split writes its k best to the workspace, topk_merge_kernel folds them.
 //
 // pic_build: CSR of W = A + A^T, A_ij = exp(-d2_ij / sigma^2) for j in row i's list (fp64 from the fp32 distance): count
 //   in-degrees (integer atomics), scan, scatter (out-edges at fixed slots, in-edges through an integer cursor), then each
@@ -28,19 +23,12 @@
 //
 // No float atomics, no grid-wide barriers, plain launches only; the kernels initialise whatever they read of the workspace.
 #include "topk.h"
+#include "gram_tile.h"
 
 namespace {
 
-constexpr int QT = 64;               // owned rows per workgroup
-constexpr int BT = 128;              // walked rows per tile
-constexpr int KC = 32;               // feature chunk per staging step
-constexpr int RP = KC + 4;           // staging pitch (floats): 144-byte rows, 16-byte aligned float4 fragments
-constexpr int SP = BT + 4;           // Gram tile pitch (floats): 528-byte rows, 16-byte aligned float4 stores
 constexpr int KP = 64;               // list slots per row: one per lane
-constexpr int TILE_BYTES = QT * SP * 4;                  // 33,792 >= the staging buffers' (QT + BT) * RP * 4 = 27,648
-constexpr int LDS_BYTES = TILE_BYTES + QT * KP * 8;      // + the rows' lists
-constexpr int MAX_D = 4096;
-static_assert(TILE_BYTES >= (QT + BT) * RP * 4, "the Gram tile lies over the staging buffers");
+constexpr int LDS_BYTES = TILE_BYTES + QT * KP * 8;      // the Gram tile (over the staging buffers) + the rows' lists
 
 struct GraphArgs {
     const float* x;      // [n][d]
@@ -52,20 +40,6 @@ struct GraphArgs {
     int tiles, tiles_per_split;
 };
 
-// n_i = g_ii with the Gram tile's own fmaf chain: features in index order.
-__global__ __launch_bounds__(256) void graph_norm_kernel(const float* __restrict__ x, int n, int d, float* __restrict__ g) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float* r = x + i * d;
-    float acc = 0.f;
-    for (int k0 = 0; k0 < d; k0 += 4) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(r + k0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_fmaf(a[s], a[s], acc);
-    }
-    g[i] = acc;
-}
-
 __global__ __launch_bounds__(256) void graph_topk_kernel(GraphArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* Os = reinterpret_cast<float*>(smem);                      // [QT][RP] owned rows
@@ -73,74 +47,20 @@ __global__ __launch_bounds__(256) void graph_topk_kernel(GraphArgs a) {
     float* St = reinterpret_cast<float*>(smem);                      // [QT][SP], over Os / Ws once the feature loop is done
     float* Lv = reinterpret_cast<float*>(smem + TILE_BYTES);         // [QT][KP]
     int* Li = reinterpret_cast<int*>(Lv + QT * KP);                  // [QT][KP]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const long q0 = (long)blockIdx.x * QT;
-    const int n = a.n, d = a.d, k = a.k;
+    const int n = a.n, k = a.k;
 
     topk_lds_init<QT, KP, DistAscending>(Lv, Li);
 
     const int t0 = blockIdx.y * a.tiles_per_split;
     const int t1 = min(t0 + a.tiles_per_split, a.tiles);
-    const int nchunk = (d + KC - 1) / KC;
-    // staging: 4 threads per row (8 features each), rows tid / 4 + 64 v; v = 0 owned, v = 1, 2 walked
-    const int srow = tid >> 2, scol = (tid & 3) * 8;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     for (int t = t0; t < t1; ++t) {
         const long b0 = (long)t * BT;
         f32x16 acc[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tt][r] = 0.f;
-
-        f32x4 rg[3][2];
-        auto load_chunk = [&](int c) {
-            const int col = c * KC + scol;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const long gr = v == 0 ? q0 + srow : b0 + srow + 64 * (v - 1);
-                const float* p = a.x + gr * d + col;
-                rg[v][0] = (gr < n && col < d) ? *reinterpret_cast<const f32x4*>(p) : zero4;
-                rg[v][1] = (gr < n && col + 4 < d) ? *reinterpret_cast<const f32x4*>(p + 4) : zero4;
-            }
-        };
-        load_chunk(0);
-        for (int c = 0; c < nchunk; ++c) {
-            __syncthreads();                                         // previous chunk's fragments / previous tile's scan are done
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                float* dst = (v == 0 ? Os + srow * RP : Ws + (srow + 64 * (v - 1)) * RP) + scol;
-                // features 8g + {0 2 4 6} then 8g + {1 3 5 7}: lane half h of MFMA step s reads feature 8g + 2s + h
-                const f32x4 ev = {rg[v][0][0], rg[v][0][2], rg[v][1][0], rg[v][1][2]};
-                const f32x4 od = {rg[v][0][1], rg[v][0][3], rg[v][1][1], rg[v][1][3]};
-                *reinterpret_cast<f32x4*>(dst) = ev;
-                *reinterpret_cast<f32x4*>(dst + 4) = od;
-            }
-            __syncthreads();
-            if (c + 1 < nchunk) load_chunk(c + 1);
-#pragma unroll
-            for (int g = 0; g < KC / 8; ++g) {
-                const f32x4 fo = *reinterpret_cast<const f32x4*>(Os + ((w & 1) * 32 + l31) * RP + g * 8 + 4 * half);
-                const f32x4 f0 = *reinterpret_cast<const f32x4*>(Ws + ((w >> 1) * 64 + l31) * RP + g * 8 + 4 * half);
-                const f32x4 f1 = *reinterpret_cast<const f32x4*>(Ws + ((w >> 1) * 64 + 32 + l31) * RP + g * 8 + 4 * half);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f0[s], fo[s], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f1[s], fo[s], acc[1], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();                                             // all fragment reads done: the staging buffers are dead
-        // C/D map: column = lane & 31 = owned row 32 (w & 1) + .., register r = walked row 64 (w >> 1) + 32 tt + (r & 3) + 8 (r >> 2) + 4 half
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v4 = {acc[tt][4 * g], acc[tt][4 * g + 1], acc[tt][4 * g + 2], acc[tt][4 * g + 3]};
-                *reinterpret_cast<f32x4*>(St + ((w & 1) * 32 + l31) * SP + (w >> 1) * 64 + tt * 32 + 8 * g + 4 * half) = v4;
-            }
-        __syncthreads();
+        gram_tile<ChainOrder::Index>(a.x, n, a.d, q0, b0, Os, Ws, acc);      // (its first barrier: the previous tile's scan is done)
+        gram_tile_to_lds(acc, St);
 
         const long r0 = b0 + lane, r1 = b0 + 64 + lane;
         const bool ok0 = r0 < n, ok1 = r1 < n;
@@ -416,7 +336,7 @@ extern "C" int audiossl_knn_graph_l2(const float* x, int n, int d, int k, int* i
                                      void* stream) {
     GraphPlan p;
     ASSL_REQUIRE(x && idx && d2 && workspace);
-    ASSL_REQUIRE(d >= 4 && d <= MAX_D && d % 4 == 0);
+    ASSL_REQUIRE(gram_width_ok(d));
     ASSL_REQUIRE(graph_plan(n, k, p));
     ASSL_REQUIRE(workspace_bytes >= p.ws_bytes);
     if (!ASSL_ALIGNED16(x) || !ASSL_ALIGNED16(workspace)) return ASSL_EALIGN;
@@ -432,7 +352,7 @@ extern "C" int audiossl_knn_graph_l2(const float* x, int n, int d, int k, int* i
     int* wi = reinterpret_cast<int*>(wv + (long)p.splits * a.split_stride);
     a.out_v = p.splits == 1 ? d2 : wv;
     a.out_i = p.splits == 1 ? idx : wi;
-    hipLaunchKernelGGL(graph_norm_kernel, GRID1(n), dim3(256), 0, s, x, n, d, gn);
+    hipLaunchKernelGGL(gram_norm_kernel<ChainOrder::Index>, GRID1(p.n_pad), dim3(256), 0, s, x, n, d, p.n_pad, gn);
     hipLaunchKernelGGL(graph_topk_kernel, dim3((unsigned)p.q_tiles, (unsigned)p.splits), dim3(256), LDS_BYTES, s, a);
     if (p.splits > 1)
         hipLaunchKernelGGL((topk_merge_kernel<KP, DistAscending>), dim3((unsigned)(((long)n + 3) / 4)), dim3(256), 0, s, wv, wi, p.splits,

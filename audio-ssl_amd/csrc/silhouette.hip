@@ -4,12 +4,11 @@
 //   a_i = mean distance from row i to the OTHER members of its cluster, b_i = min over the other clusters of the mean distance
 //   to that cluster's members, s_i = (b_i - a_i) / max(a_i, b_i); 0 for a one-member cluster and for 0 / 0.
 //
-// It needs every pairwise distance and stores none of them.  The rows arrive SORTED BY CLUSTER (seg [K + 1] = offsets), and
-// the tile is graph.hip's: a workgroup (4 waves) owns 64 rows i and walks 128-row tiles j, g_ij = <x_i, x_j> on the fp32-input
-// MFMA (mfma_f32_32x32x2f32: an fmaf chain over d in index order), features staged through LDS in chunks of 32 with every
-// group of 8 stored interleaved; silhouette_norm_kernel runs the same chain for n_i = g_ii, so
+// It needs every pairwise distance and stores none of them.  The rows arrive SORTED BY CLUSTER (seg [K + 1] = offsets).
+// g_ij = <x_i, x_j> is the fp32 Gram tile of gram_tile.h in index chain order and n_i = g_ii its norm kernel, so
 // dist_ij = sqrt(max(0, (n_i + n_j) - 2 g_ij)) is exactly 0 wherever row j repeats row i.  Self leaves by INDEX.  sqrt is the
-// correctly rounded fp32 one (hipcc's default for sqrtf); everything after it is fp64.
+// correctly rounded fp32 one (hipcc's default for sqrtf); everything after it is fp64.  What this file adds on top of the
+// tile is the per-cluster walk:
 //
 // Reduction.  The 64 x 128 tile is dumped to LDS over the dead staging buffers and wave w takes rows 16w..16w+15: each lane
 // turns its two columns (lane, 64 + lane) of every row into distances, in place, and adds them to one fp64 accumulator per
@@ -21,20 +20,12 @@
 // column split would need per-cluster partial sums across splits.
 //
 // No atomics, no memset, plain launches; the workspace (the norms) needs no clearing; two launches agree bit for bit.
-#include "common.h"
+#include "gram_tile.h"
 
 namespace {
 
-constexpr int QT = 64;               // owned rows per workgroup
-constexpr int BT = 128;              // walked rows per tile
-constexpr int KC = 32;               // feature chunk per staging step
-constexpr int RP = KC + 4;           // staging pitch (floats): 144-byte rows, 16-byte aligned float4 fragments
-constexpr int SP = BT + 4;           // Gram tile pitch (floats): 528-byte rows, 16-byte aligned float4 stores
 constexpr int RW = QT / 4;           // rows per wave
-constexpr int TILE_BYTES = QT * SP * 4;                  // 33,792 >= the staging buffers' (QT + BT) * RP * 4 = 27,648
-constexpr int LDS_BYTES = TILE_BYTES + QT * 4;           // + the owned rows' norms
-constexpr int MAX_D = 4096;
-static_assert(TILE_BYTES >= (QT + BT) * RP * 4, "the Gram tile lies over the staging buffers");
+constexpr int LDS_BYTES = TILE_BYTES + QT * 4;           // the Gram tile (over the staging buffers) + the owned rows' norms
 
 struct SilArgs {
     const float* x;      // [n][d], rows sorted by cluster
@@ -44,20 +35,6 @@ struct SilArgs {
     int n, d, K;
     int tiles;
 };
-
-// n_i = g_ii with the Gram tile's own fmaf chain: features in index order (graph.hip's graph_norm_kernel).
-__global__ __launch_bounds__(256) void silhouette_norm_kernel(const float* __restrict__ x, int n, int d, float* __restrict__ g) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float* r = x + i * d;
-    float acc = 0.f;
-    for (int k0 = 0; k0 < d; k0 += 4) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(r + k0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_fmaf(a[s], a[s], acc);
-    }
-    g[i] = acc;
-}
 
 // The wave's RW per-lane partial sums -> every row's total: row r in lanes 4r..4r+3 (returned value).  A fixed tree.
 __device__ __forceinline__ double fold_rows(double (&v)[RW], int lane) {
@@ -82,16 +59,11 @@ __global__ __launch_bounds__(256) void silhouette_kernel(SilArgs a) {
     float* Ws = Os + QT * RP;                                        // [BT][RP] walked rows
     float* St = reinterpret_cast<float*>(smem);                      // [QT][SP], over Os / Ws once the feature loop is done
     float* Ns = reinterpret_cast<float*>(smem + TILE_BYTES);         // [QT] owned norms
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const long q0 = (long)blockIdx.x * QT;
-    const int n = a.n, d = a.d, K = a.K;
+    const int n = a.n, K = a.K;
 
     if (tid < QT) Ns[tid] = q0 + tid < n ? a.gn[q0 + tid] : 0.f;     // (the first barrier of the tile loop orders this)
-
-    const int nchunk = (d + KC - 1) / KC;
-    // staging: 4 threads per row (8 features each), rows tid / 4 + 64 v; v = 0 owned, v = 1, 2 walked
-    const int srow = tid >> 2, scol = (tid & 3) * 8;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     // the walk's state: cluster c (wave-uniform; its columns are seg[c] .. seg[c + 1] - 1), the rows' sums over the part of c
     // walked so far, and for the lane's row (lane >> 2 of this wave's 16) a, b and whether its cluster has one member
@@ -107,58 +79,8 @@ __global__ __launch_bounds__(256) void silhouette_kernel(SilArgs a) {
     for (int t = 0; t < a.tiles; ++t) {
         const long b0 = (long)t * BT;
         f32x16 acc[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tt][r] = 0.f;
-
-        f32x4 rg[3][2];
-        auto load_chunk = [&](int ch) {
-            const int col = ch * KC + scol;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const long gr = v == 0 ? q0 + srow : b0 + srow + 64 * (v - 1);
-                const float* p = a.x + gr * d + col;
-                rg[v][0] = (gr < n && col < d) ? *reinterpret_cast<const f32x4*>(p) : zero4;
-                rg[v][1] = (gr < n && col + 4 < d) ? *reinterpret_cast<const f32x4*>(p + 4) : zero4;
-            }
-        };
-        load_chunk(0);
-        for (int ch = 0; ch < nchunk; ++ch) {
-            __syncthreads();                                         // previous chunk's fragments / previous tile's scan are done
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                float* dst = (v == 0 ? Os + srow * RP : Ws + (srow + 64 * (v - 1)) * RP) + scol;
-                // features 8g + {0 2 4 6} then 8g + {1 3 5 7}: lane half h of MFMA step s reads feature 8g + 2s + h
-                const f32x4 ev = {rg[v][0][0], rg[v][0][2], rg[v][1][0], rg[v][1][2]};
-                const f32x4 od = {rg[v][0][1], rg[v][0][3], rg[v][1][1], rg[v][1][3]};
-                *reinterpret_cast<f32x4*>(dst) = ev;
-                *reinterpret_cast<f32x4*>(dst + 4) = od;
-            }
-            __syncthreads();
-            if (ch + 1 < nchunk) load_chunk(ch + 1);
-#pragma unroll
-            for (int g = 0; g < KC / 8; ++g) {
-                const f32x4 fo = *reinterpret_cast<const f32x4*>(Os + ((w & 1) * 32 + l31) * RP + g * 8 + 4 * half);
-                const f32x4 f0 = *reinterpret_cast<const f32x4*>(Ws + ((w >> 1) * 64 + l31) * RP + g * 8 + 4 * half);
-                const f32x4 f1 = *reinterpret_cast<const f32x4*>(Ws + ((w >> 1) * 64 + 32 + l31) * RP + g * 8 + 4 * half);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f0[s], fo[s], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f1[s], fo[s], acc[1], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();                                             // all fragment reads done: the staging buffers are dead
-        // C/D map: column = lane & 31 = owned row 32 (w & 1) + .., register r = walked row 64 (w >> 1) + 32 tt + (r & 3) + 8 (r >> 2) + 4 half
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v4 = {acc[tt][4 * g], acc[tt][4 * g + 1], acc[tt][4 * g + 2], acc[tt][4 * g + 3]};
-                *reinterpret_cast<f32x4*>(St + ((w & 1) * 32 + l31) * SP + (w >> 1) * 64 + tt * 32 + 8 * g + 4 * half) = v4;
-            }
-        __syncthreads();
+        gram_tile<ChainOrder::Index>(a.x, n, a.d, q0, b0, Os, Ws, acc);      // (its first barrier: the previous tile's walk is done)
+        gram_tile_to_lds(acc, St);
 
         // this wave's 16 rows x the lane's two columns -> distances; a column past n or the row itself contributes 0
         const long r0 = b0 + lane, r1 = b0 + 64 + lane;
@@ -236,7 +158,7 @@ extern "C" int audiossl_silhouette(const float* xs, int n, int d, const int* seg
     int tiles;
     ASSL_REQUIRE(xs && seg && seg_host && s && workspace);
     ASSL_REQUIRE(sil_plan(n, q_tiles, tiles, ws));
-    ASSL_REQUIRE(d >= 4 && d <= MAX_D && d % 4 == 0);
+    ASSL_REQUIRE(gram_width_ok(d));
     ASSL_REQUIRE(K >= 2 && K <= n - 1);
     ASSL_REQUIRE(workspace_bytes >= ws);
     ASSL_REQUIRE(seg_host[0] == 0 && seg_host[K] == n);
@@ -248,7 +170,7 @@ extern "C" int audiossl_silhouette(const float* xs, int n, int d, const int* seg
     a.x = xs; a.gn = gn; a.seg = seg; a.s = s;
     a.n = n; a.d = d; a.K = K;
     a.tiles = tiles;
-    hipLaunchKernelGGL(silhouette_norm_kernel, GRID1(n), dim3(256), 0, st, xs, n, d, gn);
+    hipLaunchKernelGGL(gram_norm_kernel<ChainOrder::Index>, GRID1(q_tiles * QT), dim3(256), 0, st, xs, n, d, q_tiles * QT, gn);
     hipLaunchKernelGGL(silhouette_kernel, dim3((unsigned)q_tiles), dim3(256), LDS_BYTES, st, a);
     ASSL_LAUNCH_CHECK();
 }
