@@ -37,7 +37,8 @@ def main(args):
     def features(checkpoint, upstream):
         embedder = load_embedder(checkpoint, upstream, layer=layers)
         duration = args.duration or float(embedder.model.config["pretrain"]["input"]["length_wave"])
-        return extract_embeddings(embedder, files, batch_size=args.batch_size, window="center", duration=duration)
+        return extract_embeddings(embedder, files, batch_size=args.batch_size, window=args.window, duration=duration,
+                                  max_duration=args.max_duration)
 
     feats_a = features(args.checkpoint, args.upstream)
     feats_b = features(args.checkpoint_b, args.upstream_b or args.upstream) if args.checkpoint_b else None
@@ -60,6 +61,9 @@ def get_args(argv=None):
     parser.add_argument("--batch_size", type=int, default=64)
     parser.add_argument("--duration", type=float, default=None, help="seconds per clip (default: the checkpoint's length_wave)")
     parser.add_argument("--max_files", type=int, default=None)
+    parser.add_argument("--window", choices=("center", "whole"), default="center",
+                        help="whole: every clip at its own length, in ragged batches (conv encoder)")
+    parser.add_argument("--max_duration", type=float, default=30.0, help="--window whole: longer clips are centre-cropped to this many seconds")
     return parser.parse_args(argv)
 
 

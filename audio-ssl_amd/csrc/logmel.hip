@@ -53,6 +53,7 @@ struct LogmelArgs {
     const int* mel_start;    // [n_mels] first bin of the run
     float eps_pow, eps_log;
     int apply_log;           // 0: return the mel power (MelSpectrogramLibrosa.__call__), 1: log(mel + eps_log)
+    const int* lens;         // ragged form only: [B] samples of each clip (rows are L apart, out rows T apart); else nullptr
 };
 
 __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
@@ -198,7 +199,12 @@ constexpr int OTF = 32, OTP = OTF + 1;  // frames per tile; row pitch in floats 
 // (OTF = 16: 64-byte segments at the 404-byte row pitch of T = 101 straddle three 32-byte sectors - 23.1 MB left the L2 for 13.2 MB
 // of output; at B = 512 a wave's run is 25-26 frames of one clip, so 32 columns give ONE flush of ~100-byte segments per run)
 
-template <int MPL, int NCH>
+// RAGGED: clip b has lens[b] samples in a row of L and T_b = 1 + lens[b] / hop frames of its own (reflected at ITS end); the frames
+// of all clips are numbered one after the other (total_frames = sum T_b), so no wave transforms a padded frame.  The wave that
+// finishes a clip writes zeros over out[b][.][T_b .. T): a tail frame costs a store, not an FFT.
+struct FrameCur { int b, t, Tb, Lb; };                       // clip, frame in the clip, frames and samples of that clip (wave-uniform)
+
+template <int MPL, int NCH, bool RAGGED>
 __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_frames) {
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -238,12 +244,44 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
     // clip / frame split and the interior-or-border choice are scalar code
     const int gw = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), nw = gridDim.x * 4;
     const int f0 = (int)((long)gw * total_frames / nw), f1 = (int)((long)(gw + 1) * total_frames / nw);
-    // raw samples of frame f: z[m] = x[2m] + i x[2m+1], m = lane + 64 r (reflected at the clip borders)
-    auto load_frame = [&](int f, v2 (&z)[8]) {
-        const int b = f / a.T, t = f - b * a.T;
-        const float* x = a.wave + (long)b * a.L;
-        const int base = t * a.hop - NFFT / 2;
-        if (base >= 0 && base + NFFT <= a.L) {               // interior frame: eight coalesced float2 per lane
+    // length and frames of clip c.b (ragged form).  The host checked its copy of lens before the launch; the clamps keep a stale
+    // device copy inside the row and the output all the same
+    auto enter = [&](FrameCur& c) {
+        c.Lb = min(max(a.lens[c.b], NFFT), a.L);
+        c.Tb = min(1 + c.Lb / a.hop, a.T);
+    };
+    // where frame f lies: a division for the rectangle; the ragged form walks the clips once to its first frame and steps after that
+    auto locate = [&](int f) {
+        if constexpr (RAGGED) {
+            FrameCur c{0, f, 0, 0};
+            for (;; ++c.b) {
+                enter(c);
+                if (c.t < c.Tb) return c;
+                if (c.b == a.B - 1) { c.t = c.Tb - 1; return c; }
+                c.t -= c.Tb;
+            }
+        } else {
+            const int b = f / a.T;
+            return FrameCur{b, f - b * a.T, a.T, a.L};
+        }
+    };
+    auto step = [&](FrameCur c, int f) {                     // c is frame f - 1 -> frame f (f < total_frames)
+        if constexpr (RAGGED) {
+            if (++c.t == c.Tb) {
+                if (c.b == a.B - 1) { --c.t; return c; }
+                ++c.b; c.t = 0;
+                enter(c);
+            }
+            return c;
+        } else {
+            return locate(f);
+        }
+    };
+    // raw samples of a frame: z[m] = x[2m] + i x[2m+1], m = lane + 64 r (reflected at the clip borders)
+    auto load_frame = [&](const FrameCur& c, v2 (&z)[8]) {
+        const float* x = a.wave + (long)c.b * a.L;
+        const int base = c.t * a.hop - NFFT / 2;
+        if (base >= 0 && base + NFFT <= c.Lb) {              // interior frame: eight coalesced float2 per lane
             const v2* src = reinterpret_cast<const v2*>(x + base);
 #pragma unroll
             for (int r = 0; r < 8; ++r) z[r] = src[lane + 64 * r];
@@ -251,21 +289,23 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 int p0 = base + 2 * (lane + 64 * r), p1 = p0 + 1;
-                p0 = p0 < 0 ? -p0 : (p0 >= a.L ? 2 * (a.L - 1) - p0 : p0);
-                p1 = p1 < 0 ? -p1 : (p1 >= a.L ? 2 * (a.L - 1) - p1 : p1);
+                p0 = p0 < 0 ? -p0 : (p0 >= c.Lb ? 2 * (c.Lb - 1) - p0 : p0);
+                p1 = p1 < 0 ? -p1 : (p1 >= c.Lb ? 2 * (c.Lb - 1) - p1 : p1);
                 z[r] = v2{x[p0], x[p1]};
             }
         }
     };
     v2 nxt[8];
-    if (f0 < f1) load_frame(f0, nxt);
+    FrameCur cn{0, 0, 0, 0};
+    if (f0 < f1) { cn = locate(f0); load_frame(cn, nxt); }
     int tl = 0;                                              // column of the output tile the current frame goes to (wave-uniform)
     for (int f = f0; f < f1; ++f) {
-        const int b = f / a.T, t = f - b * a.T;
+        const FrameCur cur = cn;
+        const int b = cur.b, t = cur.t;
         v2 v[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = nxt[r] * win[r];
-        if (f + 1 < f1) load_frame(f + 1, nxt);              // the next frame's samples travel while this frame is transformed
+        if (f + 1 < f1) { cn = step(cur, f + 1); load_frame(cn, nxt); }   // the next frame's samples travel while this frame is transformed
         // ---- pass 0 (Ns = 1)
         dft8v(v);
         wave_fence();
@@ -318,7 +358,7 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
         wave_fence();
         // ---- flush the tile when it is full, at the end of a clip (the next frame belongs to another clip's rows) and at the
         //      end of the run: frames t - tl .. t of clip b, OTF lanes per mel row
-        if (tl == OTF - 1 || t == a.T - 1 || f == f1 - 1) {
+        if (tl == OTF - 1 || t == cur.Tb - 1 || f == f1 - 1) {
             const int col = lane & (OTF - 1), t0 = t - tl;
             float* const dst = a.out + (long)b * a.n_mels * a.T + t0 + col;
             constexpr int RPI = 64 / OTF;                    // mel rows per store instruction
@@ -327,6 +367,13 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
                 const int row = RPI * i + lane / OTF;
                 const float v = ot[row * OTP + col];
                 if (col <= tl && row < a.n_mels) dst[(long)row * a.T] = v;
+            }
+            if constexpr (RAGGED) {
+                if (t == cur.Tb - 1) {                       // the clip is done: zeros over its tail frames, row by row
+                    float* const z0 = a.out + (long)b * a.n_mels * a.T;
+                    for (int row = 0; row < a.n_mels; ++row)
+                        for (int c = cur.Tb + lane; c < a.T; c += 64) z0[(long)row * a.T + c] = 0.f;
+                }
             }
             wave_fence();
             tl = 0;
@@ -347,7 +394,7 @@ extern "C" int audiossl_logmel_fwd(const float* wave, float* out, int B, int L, 
     ASSL_REQUIRE(T == 1 + L / hop);
     const size_t dyn = sizeof(float) * ((size_t)n_mels * taps + (size_t)n_mels * (FPB + 1));
     ASSL_REQUIRE(dyn <= 28 * 1024);
-    LogmelArgs a{wave, out, B, L, T, hop, n_mels, taps, win, tw, melw, mel_start, eps_pow, eps_log, apply_log};
+    LogmelArgs a{wave, out, B, L, T, hop, n_mels, taps, win, tw, melw, mel_start, eps_pow, eps_log, apply_log, nullptr};
     // the persistent form needs 8-byte aligned frame starts and mel rows that fit its register budget
     static const int v1_only = getenv("AUDIOSSL_LOGMEL_V1") ? atoi(getenv("AUDIOSSL_LOGMEL_V1")) : 0;
     const bool v2_ok = !v1_only && hop % 2 == 0 && L % 2 == 0 && (((uintptr_t)wave) & 7) == 0 && L >= NFFT;
@@ -355,10 +402,39 @@ extern "C" int audiossl_logmel_fwd(const float* wave, float* out, int B, int L, 
         const long total = (long)B * T;
         const int blocks = (int)min((long)512, (total + 3) / 4);          // two workgroups per CU, ~25 frames per wave at B = 512
         const size_t lds = sizeof(float) * 4 * (2 * EXW + PWW + 64 * (n_mels <= 64 ? 1 : 2) * OTP);
-        if (n_mels <= 64) hipLaunchKernelGGL((logmel2_kernel<1, 13>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
-        else              hipLaunchKernelGGL((logmel2_kernel<2, 7>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
+        if (n_mels <= 64) hipLaunchKernelGGL((logmel2_kernel<1, 13, false>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
+        else              hipLaunchKernelGGL((logmel2_kernel<2, 7, false>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
         ASSL_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(logmel_kernel, dim3(ceil_div(T, FPB), B), dim3(256), dyn, static_cast<hipStream_t>(stream), a);
+    ASSL_LAUNCH_CHECK();
+}
+
+// Ragged batch: wave [B][Lmax] with lens[b] real samples at the head of row b (what follows them is never read), out [B][n_mels][Tmax]
+// with frames t < 1 + lens[b] / hop computed from clip b alone and exact zeros after them.  lens_host is the caller's host copy of
+// lens: every length is checked before the launch.  Runs on the persistent kernel only.
+extern "C" int audiossl_logmel_ragged_fwd(const float* wave, const int* lens, const int* lens_host, float* out, int B, int Lmax, int Tmax,
+                                          int n_fft, int hop, int n_mels, int taps, const float* win, const float* tw, const float* melw,
+                                          const int* mel_start, float eps_pow, float eps_log, int apply_log, void* stream) {
+    ASSL_REQUIRE(wave && lens && lens_host && out && win && tw && melw && mel_start);
+    ASSL_REQUIRE(n_fft == NFFT);
+    ASSL_REQUIRE(B > 0 && hop > 0 && hop % 2 == 0 && Lmax > 0 && Lmax % 2 == 0 && Tmax > 0 && n_mels > 0 && n_mels <= 128 && taps > 0);
+    ASSL_REQUIRE(n_mels <= 64 ? taps + 3 <= 52 : taps + 3 <= 28);          // the mel rows fit the kernel's registers
+    constexpr int MIN_LEN = 1120;      // 8 frames at hop 160: one row after three pools; > n_fft / 2, so a reflection stays inside the clip
+    long total = 0;
+    int longest = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = lens_host[b];
+        ASSL_REQUIRE(n >= MIN_LEN && n <= Lmax);
+        longest = max(longest, n);
+        total += 1 + n / hop;
+    }
+    ASSL_REQUIRE(Tmax >= 1 + longest / hop && total < (1l << 31) && (long)B * Tmax < (1l << 31));
+    if ((((uintptr_t)wave) & 7) != 0) return ASSL_EALIGN;                  // interior frames are read as float2
+    LogmelArgs a{wave, out, B, Lmax, Tmax, hop, n_mels, taps, win, tw, melw, mel_start, eps_pow, eps_log, apply_log, lens};
+    const int blocks = (int)min((long)512, (total + 3) / 4);
+    const size_t lds = sizeof(float) * 4 * (2 * EXW + PWW + 64 * (n_mels <= 64 ? 1 : 2) * OTP);
+    if (n_mels <= 64) hipLaunchKernelGGL((logmel2_kernel<1, 13, true>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
+    else              hipLaunchKernelGGL((logmel2_kernel<2, 7, true>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
     ASSL_LAUNCH_CHECK();
 }

@@ -6,7 +6,8 @@ data, nothing is trained.
     python audio-ssl_amd/evaluate_knn.py --checkpoint final.ckpt --upstream delores_m --train_csv train.csv --test_csv test.csv
 
 The CSVs are `train_downstream.py`'s (`wav,label`); label ids are sorted as `DownstreamDataset` sorts them.  Prints one JSON
-line: {"top1", "k", "T", "N_train", "N_test", "d"}.  Single GPU.
+line: {"top1", "k", "T", "N_train", "N_test", "d"}.  `--window whole` embeds every clip at its own length (up to `--max_duration`
+seconds) instead of one `length_wave` window per file.  Single GPU.
 """
 import argparse
 import json
@@ -38,7 +39,7 @@ def main(args):
         raise ValueError(f"labels of {args.test_csv} that {args.train_csv} does not have: {unknown[:5]}")
     embedder = load_embedder(args.checkpoint, args.upstream, config=config, layer=args.layer)
     duration = float(embedder.model.config["pretrain"]["input"]["length_wave"])
-    kw = dict(batch_size=args.batch_size, window=args.window, duration=duration)
+    kw = dict(batch_size=args.batch_size, window=args.window, duration=duration, max_duration=args.max_duration)
     bank = extract_embeddings(embedder, list(train["wav"]), **kw)
     queries = extract_embeddings(embedder, list(test["wav"]), **kw)
     y_train = torch.tensor([label2id[v] for v in train["label"]], dtype=torch.int64)
@@ -65,7 +66,9 @@ def get_args(argv=None):
     parser.add_argument("-k", type=int, default=20)
     parser.add_argument("--temperature", type=float, default=0.07)
     parser.add_argument("--layer", choices=("backbone", "head"), default="backbone")
-    parser.add_argument("--window", choices=("center", "random"), default="center")
+    parser.add_argument("--window", choices=("center", "random", "whole"), default="center",
+                        help="whole: every clip at its own length, in ragged batches (conv encoder)")
+    parser.add_argument("--max_duration", type=float, default=30.0, help="--window whole: longer clips are centre-cropped to this many seconds")
     parser.add_argument("--batch_size", type=int, default=64)
     parser.add_argument("--dump_embeddings", metavar="DIR", default=None, help="write embeddings and labels as .npy")
     return parser.parse_args(argv)

@@ -83,3 +83,18 @@ class DownstreamFrontEnd:
     def __call__(self, waves):
         waves = _waveforms(waves.cuda(non_blocking=True))
         return extract_log_mel_spectrogram(waves.float().contiguous(), self.to_mel_spec).unsqueeze(1)
+
+    @torch.no_grad()
+    def ragged(self, waves, lens=None):
+        """Clips of different lengths: [B, Lmax] float32 with lens[b] samples at the head of row b, or a `PcmBatch` packed with
+        align=1 (its own `.lens`) -> ([B, 1, n_mels, Tmax] log-mel with zeros after each clip's frames, lens int32 on the device)."""
+        from src.dataset.ingest import PcmBatch, pcm_window
+        if isinstance(waves, PcmBatch):
+            if waves.align != 1:
+                raise ValueError("a ragged batch takes left-aligned rows: PcmBatch.pack(..., align=1)")
+            lens = waves.lens if lens is None else lens
+            waves = pcm_window(waves)
+        elif lens is None:
+            raise ValueError("lens is required with a waveform tensor")
+        x, lens_dev = self.to_mel_spec.logmel_ragged(waves.cuda(non_blocking=True), lens)
+        return x.unsqueeze(1), lens_dev

@@ -446,7 +446,7 @@ def stem_moments_pair(xa, xb=None):
 
 
 def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_running=True, want_layers=True, Wc=None,
-                    layer_out=None, before_fc=None, stem_moments=None, need_bwd=True):
+                    layer_out=None, before_fc=None, stem_moments=None, need_bwd=True, lens=None, hop=160):
     """P: dict of fp32 device tensors with the reference's state_dict keys (features_1.0.weight, ...).
     x [N,1,F,T] fp32.  keep: uint8 [N*T3, d] dropout keep-mask or None (no dropout).
     Wc: optional {"fc.0.weight", "fc.3.weight"} already in the activation dtype (flat shadow); layer_out: optional
@@ -455,6 +455,10 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     step in one launch); only where `stem_fused(dtype, train)` holds.
     need_bwd=False: no encoder_backward will follow this call (key / target encoders, no-grad and evaluation passes) - the conv
     blocks then need not store their unpooled outputs (ctx.Y2 / ctx.Y3 are None where they did not).
+    lens: int32 [N] on the device - a ragged batch (eval mode, no backward): clip n has lens[n] samples, i.e. T_n = 1 + lens[n] // hop
+    frames of x, and the front end left exact zeros after them (`logmel_ragged_fwd`); T % 8 == 0.  The pooled outputs of blocks 1 and
+    2 are zeroed from row T_n >> 1 / T_n >> 2 on, so the next convolution sees its own zero padding there, and x1, x2, x3 (fp32) are
+    means over each clip's own rows.  Rows of H2 from T_n >> 3 on are computed and meaningless: pool with `ragged_pool`.
     Returns (x1, x2, x3, H2 [N,T3,d]) in the activation dtype and the ctx for the backward."""
     Nimg, _, F, T = x.shape
     assert F == 64, "the HIP encoder is built for n_mels = 64 (the reference's only setting)"
@@ -463,6 +467,11 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     c.P = P
     c.dtype, c.N, c.F, c.T, c.train, c.p_drop = dtype, Nimg, F, T, train, p_drop
     c.need_bwd = need_bwd
+    ragged = lens is not None
+    if ragged:
+        assert not train and not need_bwd, "a ragged batch runs in eval mode without a backward (BatchNorm on running statistics)"
+        assert T % 8 == 0, "a ragged batch is padded to a multiple of 8 frames"
+        assert lens.dtype == torch.int32 and lens.is_cuda and tuple(lens.shape) == (Nimg,), "lens: int32 [N] on the device"
     img = x.reshape(Nimg, F, T).contiguous()
     c.img = img
     w1 = P["features_1.0.weight"].reshape(64, 9)
@@ -495,15 +504,19 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     c.P1 = _empty((Nimg, T1, F1, 64), td, like=x)
     x1 = x2 = x3 = None
     if want_layers:
-        x1, x2, x3 = layer_out if layer_out is not None else (_empty((Nimg, f * 64), td, like=x) for f in (F // 2, F // 4, F // 8))
-    # the MFMA stem also leaves x_1 (mean over time of its pooled output) when an fp32 buffer is wanted for it
-    x1_fused = c.stem_mfma and x1 is not None and x1.dtype == torch.float32 and x1.is_contiguous()
+        x1, x2, x3 = layer_out if layer_out is not None else (_empty((Nimg, f * 64), torch.float32 if ragged else td, like=x)
+                                                              for f in (F // 2, F // 4, F // 8))
+    # the MFMA stem also leaves x_1 (mean over time of its pooled output) when an fp32 buffer is wanted for it (never for a ragged
+    # batch: the stem's sums run over the padded rows too)
+    x1_fused = c.stem_mfma and x1 is not None and x1.dtype == torch.float32 and x1.is_contiguous() and not ragged
     x1_parts = _empty((4, Nimg, (F // 2) * 64), torch.float32, like=x) if x1_fused else None        # AUDIOSSL_CONV1_XL_PARTS
     if fused:
         N.call("conv1_fwd_train", img, Nimg, F, T, c.mom1, float(Nimg * F * T), w1, b1, g1, be1, rm1, rv1, BN_MOMENTUM, BN_EPS,
                c.sc1, c.sh1, c.mean1, c.rstd1, c.P1, x1_parts)
     else:
         N.call("conv1_fwd", dtype if (dtype == N.F32 or c.stem_mfma) else 2, img, Nimg, F, T, w1, b1, c.sc1, c.sh1, c.P1, x1_parts)
+    if ragged:
+        N.call("tail_mask", dtype, c.P1, lens, hop, 1, Nimg, T1, F1 * 64)
     col = _col_buffer(dtype, Nimg, T1, F1, x)
     bn2 = (P["features_2.1.weight"], P["features_2.1.bias"], P["features_2.1.running_mean"], P["features_2.1.running_var"])
     packs = [_empty((64, 576), td, like=x) for _ in range(4)]         # both layers' (forward, data-gradient) layouts: one launch
@@ -512,6 +525,8 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
                                                        P["features_2.0.bias"], bn2, train, update_running, col, packed=packs[:2],
                                                        keep_y=need_bwd)
     T2, F2 = T1 // 2, F1 // 2
+    if ragged:
+        N.call("tail_mask", dtype, c.P2, lens, hop, 2, Nimg, T2, F2 * 64)
     bn3 = (P["features_3.1.weight"], P["features_3.1.bias"], P["features_3.1.running_mean"], P["features_3.1.running_var"])
     c.Y3, c.P3, c.st3, c.W3f, c.W3d = _conv_block_fwd(dtype, c.P2, Nimg, T2, F2, P["features_3.0.weight"],
                                                        P["features_3.0.bias"], bn3, train, update_running, col, packed=packs[2:],
@@ -519,7 +534,10 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
     del col
     T3, F3 = T2 // 2, F2 // 2
     c.dims = (T1, F1, T2, F2, T3, F3)
-    if want_layers:
+    if want_layers and ragged:
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (x1, x2, x3)), "the ragged layer means are fp32"
+        N.call("tmean3_ragged_fwd", dtype, c.P1, x1, T1, F1, c.P2, x2, T2, F2, c.P3, x3, T3, F3, lens, hop, Nimg)
+    elif want_layers:
         o32 = int(x1.dtype == torch.float32)
         N.call("tmean3_fwd", dtype, o32, None if x1_fused else c.P1, x1, x1_parts, T1, F1, c.P2, x2, T2, F2, c.P3, x3, T3, F3, Nimg)
     d = P["fc.0.weight"].shape[0]
@@ -546,6 +564,16 @@ def encoder_forward(P, x, dtype, keep=None, p_drop=0.3, train=True, update_runni
         c.H1 = linear_fwd(dtype, c.P3, c.fw1, M, d, kin, bias=P["fc.0.bias"], relu=1, keep=c.keep, keep_scale=scale)
     c.H2 = linear_fwd(dtype, c.H1, c.fw2, M, d, d, bias=P["fc.3.bias"], relu=1)
     return x1, x2, x3, c.H2.view(Nimg, T3, d), c
+
+
+def ragged_pool(dtype, H, lens, hop=160, shift=3, want_mean=True, want_maxmean=True):
+    """H [N, Tt, D] of a ragged `encoder_forward` -> (mean, max + mean) over each clip's first (1 + lens[n] // hop) >> shift rows,
+    fp32 [N, D] each (None where not wanted), one launch."""
+    Nimg, Tt, D = H.shape
+    mean = _empty((Nimg, D), torch.float32, like=H) if want_mean else None
+    mm = _empty((Nimg, D), torch.float32, like=H) if want_maxmean else None
+    N.call("meanmax_ragged_fwd", dtype, H.contiguous(), mean, mm, lens, hop, shift, Nimg, Tt, D)
+    return mean, mm
 
 
 def _conv_block_bwd(dtype, Y, dP, dxl, st, Nimg, Ti, Fi, Pin, Wd, G_w, G_gamma, G_beta, need_dx, col, keep, dx_bf16=False, Pout=None):

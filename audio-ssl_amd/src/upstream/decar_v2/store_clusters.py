@@ -19,7 +19,8 @@ features they were computed on: the label-free answer to "is this labeling any g
 all pairs on the GPU, no distance matrix stored).  `--k_sweep 64,128,256` takes the place of `--k`: the files are embedded and
 whitened once, k-means runs for every k in the order given, one line per k reports its silhouette, and the labeling with the
 highest silhouette (a tie: the smaller k) is written; the reference has neither.
-`--window random` is the default: the reference draws `extract_window` for every clip.  Single GPU.
+`--window random` is the default: the reference draws `extract_window` for every clip; `--window whole` embeds every clip at its
+own length (up to `--max_duration` seconds).  Single GPU.
 """
 import argparse
 import sys
@@ -81,7 +82,8 @@ def main(args):
     files = list(pd.read_csv(args.input)["files"])
     embedder = load_embedder(args.checkpoint, args.upstream, config=config, layer=args.layer)
     duration = float(embedder.model.config["pretrain"]["input"]["length_wave"])
-    feats = extract_embeddings(embedder, files, batch_size=args.batch_size, window=args.window, duration=duration)
+    feats = extract_embeddings(embedder, files, batch_size=args.batch_size, window=args.window, duration=duration,
+                               max_duration=args.max_duration)
     pca = min(args.pca, feats.shape[1], max(1, len(files) - 1))                                  # rank of the covariance
     chosen = None
     if args.clustering == "pic":
@@ -141,7 +143,9 @@ def get_args(argv=None):
     parser.add_argument("--no_distribute_singletons", action="store_true", help="pic: keep one-member clusters")
     parser.add_argument("--compare", type=str, default=None, help="another `files,label` csv: print the NMI against it")
     parser.add_argument("--score", action="store_true", help="print the silhouette coefficient of the labels just written")
-    parser.add_argument("--window", choices=("center", "random"), default="random")
+    parser.add_argument("--window", choices=("center", "random", "whole"), default="random",
+                        help="whole: every clip at its own length, in ragged batches (conv encoder)")
+    parser.add_argument("--max_duration", type=float, default=30.0, help="--window whole: longer clips are centre-cropped to this many seconds")
     parser.add_argument("--layer", choices=("backbone", "head"), default="backbone")
     parser.add_argument("--batch_size", type=int, default=64)
     parser.add_argument("-c", "--config", metavar="CONFIG_PATH", default=None)

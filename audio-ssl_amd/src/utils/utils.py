@@ -126,6 +126,32 @@ class MelSpectrogramLibrosa:
         """[B, L] (or [L]) float32 waveform -> log(mel + eps) [B, n_mels, T]."""
         return self._run(wave, True)
 
+    def ragged_frames(self, max_samples):
+        """Frames a ragged batch is padded to: those of its longest clip, rounded up to the 8 that three pools divide by."""
+        return -(-self.n_frames(int(max_samples)) // 8) * 8
+
+    def logmel_ragged(self, wave, lens, n_frames=None):
+        """Clips of different lengths in one batch: wave [B, Lmax] float32 on the device with lens[b] samples at the head of row b
+        (what follows them is never read), lens int32 [B] on the HOST.  -> (log-mel [B, n_mels, Tmax], lens on the device): frames
+        t < 1 + lens[b] // shift are those of clip b alone, frames after them exact zeros.  Tmax = n_frames or `ragged_frames`."""
+        if not wave.is_cuda:
+            raise RuntimeError("audiossl HIP kernels need device tensors (no CPU fallback exists)")
+        lens_host = torch.as_tensor(lens, dtype=torch.int32).cpu().contiguous()
+        wave = wave.float()
+        if wave.shape[1] % 2:                              # interior frames are read as float2
+            wave = F.pad(wave, (0, 1))
+        wave = wave.contiguous()
+        B, L = wave.shape
+        if tuple(lens_host.shape) != (B,):
+            raise ValueError(f"lens must hold one length per row: {tuple(lens_host.shape)} for {B} rows")
+        T = int(n_frames) if n_frames is not None else self.ragged_frames(int(lens_host.max()))
+        lens_dev = lens_host.to(wave.device)
+        out = torch.empty(B, self.n_mels, T, dtype=torch.float32, device=wave.device)
+        win, tw, packed, starts = self._tables(wave.device)
+        N.call("logmel_ragged_fwd", wave, lens_dev, lens_host.data_ptr(), out, B, L, T, self.n_fft, self.shift, self.n_mels,
+               packed.shape[1], win, tw, packed, starts, np.float32(F64_EPS).item(), F32_EPS, 1)
+        return out, lens_dev
+
 
 def extract_log_mel_spectrogram(waveform, to_mel_spec):
     """waveform [L] or [B, L] -> log-mel, one fused launch."""

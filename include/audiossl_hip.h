@@ -43,6 +43,14 @@ extern "C" {
 int audiossl_logmel_fwd(const float* wave, float* out, int B, int L, int T, int n_fft, int hop, int n_mels, int taps,
                         const float* win, const float* tw, const float* melw, const int* mel_start, float eps_pow,
                         float eps_log, int apply_log, void* stream);
+/* Ragged batch (whole-clip embeddings): wave [B][Lmax] holds lens[b] samples at the head of row b (the rest
+ * of the row is never read), out [B][n_mels][Tmax].  Frames t < 1 + lens[b]/hop are those of clip b alone, the centre reflection
+ * taken at the clip's own end; frames after them are exact zeros (a store each, no FFT).  lens: int32 [B] on the device; lens_host
+ * (required): the caller's HOST copy, checked before the launch - EINVAL unless 1120 <= lens_host[b] <= Lmax for every b and
+ * Tmax >= 1 + max(lens)/hop.  hop and Lmax even, wave 8-byte aligned (EALIGN); tables as for logmel_fwd. */
+int audiossl_logmel_ragged_fwd(const float* wave, const int* lens, const int* lens_host, float* out, int B, int Lmax, int Tmax,
+                               int n_fft, int hop, int n_mels, int taps, const float* win, const float* tw, const float* melw,
+                               const int* mel_start, float eps_pow, float eps_log, int apply_log, void* stream);
 
 /* ---- K1b Kaldi fbank front end of the MAST loader: extras/mast_new/mast/dataloader.py:129-130 (kaldi.fbank, htk_compat,
  * hanning, dither 0), :132-142 (cut / zero-pad to target_length), :187-202 (FrequencyMasking, TimeMasking, (x - mean) / (2 std)),
@@ -323,6 +331,19 @@ int audiossl_gemm_multi_barlow(int count, int D, const int* K, float alpha, cons
 int audiossl_maxmean_fwd(int dtype, int out_f32, const void* H, void* y, uint8_t* arg, int N, int Tt, int D, void* stream);
 int audiossl_maxmean_bwd(int dtype, int gdtype, const void* dy, const uint8_t* arg, const void* H, void* dA, int N, int Tt,
                          int D, void* stream);
+
+/* ---- ragged batches through the conv encoder, eval mode only (csrc/ragged.hip) --------------------------
+ * Clip n of a padded batch has T_n = 1 + lens[n]/hop frames; lens: the batch's int32 [N] sample counts on the device.
+ * tail_mask: P [N][To][row_elems] of `dtype`, in place - rows t >= T_n >> shift become zeros with 16-byte stores, rows below are
+ *   neither read nor written.  P and a row must be multiples of 16 bytes (EALIGN).
+ * tmean3_ragged_fwd: x_l [N][Fo_l*64] fp32 = mean over the first T_n >> l rows of P_l [N][To_l][Fo_l][64], l = 1, 2, 3.
+ * meanmax_ragged_fwd: H [N][Tt][D] -> mean [N][D] and maxmean [N][D] = max + mean, fp32, over the first T_n >> shift rows; either
+ *   output may be NULL; any Tt (no arg-max is kept: nothing runs backward through it); D % 8 == 0. */
+int audiossl_tail_mask(int dtype, void* P, const int* lens, int hop, int shift, int N, int To, long row_elems, void* stream);
+int audiossl_tmean3_ragged_fwd(int dtype, const void* P1, float* x1, int To1, int Fo1, const void* P2, float* x2, int To2, int Fo2,
+                               const void* P3, float* x3, int To3, int Fo3, const int* lens, int hop, int N, void* stream);
+int audiossl_meanmax_ragged_fwd(int dtype, const void* H, float* mean, float* maxmean, const int* lens, int hop, int shift, int N,
+                                int Tt, int D, void* stream);
 
 /* ---- K10/K11 Barlow head: delores_s/upstream_expert.py:11-46, src/utils/utils.py:185-189 ------------------
  * colbn_fwd: h = act(scale_g*a+shift_g) on [G][M][C].  colbn_bwd: BatchNorm1d(train) backward per group (tmp = 2*G*C
