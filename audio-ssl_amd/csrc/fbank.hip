@@ -8,50 +8,26 @@
 // 512, and the 256 power bins below Nyquist go through an un-normalised HTK-scale bank into log(max(e, eps)).
 //
 // One 64-lane wave owns TWO consecutive frames of a clip at a time: both are real, so they travel as the real and the imaginary
-// part of one 512-point complex transform (the three radix-8 Stockham passes of logmel.hip, 8 points per lane) and are separated
+// part of one 512-point complex transform (the wave-level radix-8 Stockham FFT of wave_fft.h, 8 points per lane) and are separated
 // by the conjugate-mirror identity  Xa[k] = (Z[k] + conj Z[512-k]) / 2,  Xb[k] = (Z[k] - conj Z[512-k]) / 2i  - no twiddle in
 // the split, half a 512-point transform per frame.  Cross-talk between the two frames is one rounding of the larger one
 // (~1e-7 relative in amplitude), far inside the per-clip power tolerance the log-mel tests use; frames of different clips never
-// share a transform.  As in the persistent log-mel kernel, window, twiddles and the wave's mel rows (a lane is a mel row, two rows
-// per lane at 128 bins) stay in registers for the whole launch, the mirror operand comes from ds_bpermute, the waves of a block
-// never synchronise, and the next pair's samples are in flight while the current pair is transformed.
+// share a transform.  Transform, mirror fetch (ds_bpermute), register mel rows (a lane is a mel row, two rows per lane at 128 bins)
+// and the tile flush are those of wave_fft.h, shared with the persistent log-mel kernel: window, twiddles and mel rows stay in
+// registers for the whole launch, the waves of a block never synchronise, and the next pair's samples are in flight while the
+// current pair is transformed.
 // The tail (padding, masks, normalisation) is applied to the value in the register; the default [B][1][n_mels][T] layout is
 // staged through an LDS tile and leaves as 64-byte row segments, the reference's [B][T][n_mels] leaves as 256-byte rows.
 // HBM roofline: 4*L bytes read + 4*n_mels*T_target bytes written per clip.
-#include "common.h"
+#include "wave_fft.h"
 
 namespace {
 
 constexpr int NFFT = 512;               // real FFT length; the complex transform of a frame pair has as many points
-constexpr int EXW = 576;                // float2 exchange buffer of a wave (512 + 512 / 8 padding)
 constexpr int PWW = 288;                // floats: 256 power bins + zero tail up to the last aligned mel chunk (252 + 4 * 8)
 constexpr int OTF = 16, OTP = OTF + 1;  // frames per output tile; odd row pitch: the per-frame column writes are conflict-free
 constexpr int MROWS = 128;              // mel rows a wave can own (two per lane)
 constexpr int WAVE_LDS = 2 * EXW + 2 * PWW + MROWS * OTP;    // floats
-
-__device__ __forceinline__ int pidx(int a) { return a + (a >> 3); }
-
-typedef float v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2 cmulv(v2 a, v2 b) { return v2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ v2 mulmi(v2 a) { return v2{a.y, -a.x}; }     // * (-i)
-// 8-point forward DFT, natural order in / out.
-__device__ __forceinline__ void dft8v(v2* v) {
-    const float s = 0.70710678118654752440f;
-    v2 a0 = v[0] + v[4], a1 = v[0] - v[4];
-    v2 a2 = v[2] + v[6], a3 = mulmi(v[2] - v[6]);
-    v2 a4 = v[1] + v[5], a5 = v[1] - v[5];
-    v2 a6 = v[3] + v[7], a7 = mulmi(v[3] - v[7]);
-    v2 b0 = a0 + a2, b2 = a0 - a2, b1 = a1 + a3, b3 = a1 - a3;
-    v2 b4 = a4 + a6, b6 = mulmi(a4 - a6);
-    v2 t5 = a5 + a7, t7 = a5 - a7;
-    v2 b5 = v2{(t5.x + t5.y) * s, (t5.y - t5.x) * s};          // * e^{-i pi/4}
-    v2 b7 = v2{(t7.y - t7.x) * s, (-t7.x - t7.y) * s};         // * e^{-3i pi/4}
-    v[0] = b0 + b4; v[4] = b0 - b4;
-    v[1] = b1 + b5; v[5] = b1 - b5;
-    v[2] = b2 + b6; v[6] = b2 - b6;
-    v[3] = b3 + b7; v[7] = b3 - b7;
-}
-__device__ __forceinline__ void wave_fence() { asm volatile("" ::: "memory"); }     // LDS is in-order per wave: only the compiler must not reorder
 
 struct FbankArgs {
     const float* wave; const int* lens; const int* partner; const float* lam; const float* clip_mean; const int* bands; float* out;
@@ -95,29 +71,14 @@ __global__ __launch_bounds__(256, 2) void fbank_kernel(FbankArgs a, int P, int t
     // ---- per-lane constants
     float win[8];
     v2 tw1[8], tw2[8];
-    const v2* twt = reinterpret_cast<const v2*>(a.tw);
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int i = lane + 64 * r;
         win[r] = i < a.win_len ? a.win[i] : 0.f;
-        tw1[r] = twt[8 * r * (lane & 7)];                    // W_64^{r k}
-        tw2[r] = twt[r * lane];                              // W_512^{r k}
     }
-    float mw[MPL][4 * NCH];
-    int ma[MPL];
-#pragma unroll
-    for (int q = 0; q < MPL; ++q) {
-        const int m = lane + 64 * q;
-        const int st = m < a.n_mels ? min(max(a.mel_start[m], 0), 255) : 0;
-        ma[q] = st & ~3;
-#pragma unroll
-        for (int j = 0; j < 4 * NCH; ++j) {
-            const int i = ma[q] + j - st;
-            mw[q][j] = (m < a.n_mels && i >= 0 && i < a.taps) ? a.melw[m * a.taps + i] : 0.f;
-        }
-    }
-    const int mirror = ((64 - lane) & 63) * 4;               // ds_bpermute source lane (bytes)
-    const int j0 = (lane >> 3) * 64 + (lane & 7);
+    wave_fft_twiddles<1>(a.tw, lane, tw1, tw2);
+    MelRows<MPL, NCH> mel;
+    mel.load(a.melw, a.mel_start, a.n_mels, a.taps, NFFT / 2 - 1, lane);
     const float fn = (float)a.win_len;
 
     // pair range of this wave (wave-uniform, scalar registers)
@@ -179,37 +140,11 @@ __global__ __launch_bounds__(256, 2) void fbank_kernel(FbankArgs a, int P, int t
                 v[r] = v2{(da - a.preemph * dpa) * win[r], (db - a.preemph * dpb) * win[r]};
             }
             if (p + 1 < p1) load_pair(p + 1, nxa, nxpa, nxb, nxpb);      // the next pair's samples travel while this one is transformed
-            // ---- pass 0 (Ns = 1)
-            dft8v(v);
-            wave_fence();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) ex[pidx(8 * lane + r)] = v[r];
-            wave_fence();
-            // ---- pass 1 (Ns = 8)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = ex[pidx(lane + 64 * r)];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) v[r] = cmulv(v[r], tw1[r]);
-            dft8v(v);
-            wave_fence();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) ex[pidx(j0 + 8 * r)] = v[r];
-            wave_fence();
-            // ---- pass 2 (Ns = 64): Z[lane + 64 r]
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = ex[pidx(lane + 64 * r)];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) v[r] = cmulv(v[r], tw2[r]);
-            dft8v(v);
-            // ---- separate the two real spectra, bins 0..255; Z[512 - k] sits in lane 64 - lane, register 7 - r (lane 0: its own
-            //      register 8 - r)
+            wave_fft512(v, ex, lane, tw1, tw2);
+            // ---- separate the two real spectra, bins 0..255
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const v2 own = v[(8 - r) & 7], oth = v[7 - r];
-                v2 zm;
-                zm.x = __int_as_float(__builtin_amdgcn_ds_bpermute(mirror, __float_as_int(oth.x)));
-                zm.y = __int_as_float(__builtin_amdgcn_ds_bpermute(mirror, __float_as_int(oth.y)));
-                if (lane == 0) zm = own;
+                const v2 zm = wave_fft_mirror(v, r, lane);
                 const v2 A = v[r], Bc = v2{zm.x, -zm.y};
                 const v2 S = A + Bc, D = A - Bc;
                 pw0[lane + 64 * r] = 0.25f * (S.x * S.x + S.y * S.y);
@@ -219,16 +154,10 @@ __global__ __launch_bounds__(256, 2) void fbank_kernel(FbankArgs a, int P, int t
             // ---- mel rows: aligned 16-byte chunks of the power spectra against register weights, then log(max(., eps))
 #pragma unroll
             for (int q = 0; q < MPL; ++q) {
-                float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(pw0 + ma[q] + 4 * c);
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(pw1 + ma[q] + 4 * c);
-                    acc0 += mw[q][4 * c] * u[0] + mw[q][4 * c + 1] * u[1] + mw[q][4 * c + 2] * u[2] + mw[q][4 * c + 3] * u[3];
-                    acc1 += mw[q][4 * c] * w[0] + mw[q][4 * c + 1] * w[1] + mw[q][4 * c + 2] * w[2] + mw[q][4 * c + 3] * w[3];
-                }
-                val[q][0] = logf(fmaxf(acc0, a.eps));
-                val[q][1] = t + 1 < nv ? logf(fmaxf(acc1, a.eps)) : 0.f;
+                float acc[2];
+                mel.dot(q, {pw0, pw1}, acc);
+                val[q][0] = logf(fmaxf(acc[0], a.eps));
+                val[q][1] = t + 1 < nv ? logf(fmaxf(acc[1], a.eps)) : 0.f;
             }
             wave_fence();
         } else if (p + 1 < p1) {
@@ -257,18 +186,11 @@ __global__ __launch_bounds__(256, 2) void fbank_kernel(FbankArgs a, int P, int t
         }
         if (a.time_major) continue;
         wave_fence();
-        // ---- flush the tile when it is full, at the end of a clip and at the end of the run: frames t - tl .. t + 1 of clip b,
-        //      OTF lanes per mel row, 4 rows per store instruction
+        // ---- flush the tile when it is full, at the end of a clip and at the end of the run: frames t - tl .. t + 1 of clip b
+        //      (an odd T ends on a half pair: columns past T stay behind)
         if (tl + 2 == OTF || pp == P - 1 || p == p1 - 1) {
-            const int col = lane & (OTF - 1), t0 = t - tl;
-            float* const dst = a.out + (long)b * a.n_mels * a.T + t0 + col;
-            constexpr int RPI = 64 / OTF;
-#pragma unroll 4
-            for (int i = 0; i < MROWS / RPI; ++i) {
-                const int row = RPI * i + lane / OTF;
-                const float x = ot[row * OTP + col];
-                if (col < tl + 2 && t0 + col < a.T && row < a.n_mels) dst[(long)row * a.T] = x;
-            }
+            const int t0 = t - tl;
+            wave_tile_flush<OTF, MROWS>(ot, a.out + (long)b * a.n_mels * a.T + t0, min(tl + 2, a.T - t0), a.n_mels, a.T, lane);
             wave_fence();
             tl = 0;
         } else {

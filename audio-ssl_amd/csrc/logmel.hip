@@ -7,42 +7,18 @@
 // (3 passes; pass 0 straight from registers, two exchanges through padded LDS), then split into the
 // 513-bin real spectrum, squared, reduced by the sparse mel rows (<=45 taps each for the default
 // filterbank) held in LDS, and logged.  A 256-thread block handles 8 frames of one clip and writes an
-// [n_mels][8] tile so the global stores are 32-byte runs.
+// [n_mels][8] tile so the global stores are 32-byte runs.  That is logmel_kernel, the block kernel: it takes every shape.  Banks
+// that fit its register budget go to logmel2_kernel further down, one persistent wave per run of frames on the wave-level FFT of
+// wave_fft.h (shared with fbank.hip); the complex arithmetic and the 8-point DFT of both kernels come from that header.
 // HBM roofline: 4*L bytes read + 4*n_mels*T bytes written per clip (89,856 B at L=16000, T=101).
 #include <cstdlib>
-#include "common.h"
+#include "wave_fft.h"
 
 namespace {
 
 constexpr int NFFT = 1024;
 constexpr int FPB = 8;                 // frames per block
 constexpr int CPAD = 512 + 64;         // padded complex-buffer length: idx + (idx >> 3)
-
-__device__ __forceinline__ int pidx(int a) { return a + (a >> 3); }
-
-struct C32 { float x, y; };
-__device__ __forceinline__ C32 cadd(C32 a, C32 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ C32 csub(C32 a, C32 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ C32 cmul(C32 a, C32 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ C32 mul_mi(C32 a) { return {a.y, -a.x}; }     // * (-i)
-
-// 8-point forward DFT, natural order in / out.
-__device__ __forceinline__ void dft8(C32* v) {
-    const float s = 0.70710678118654752440f;
-    C32 a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]);
-    C32 a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
-    C32 a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]);
-    C32 a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
-    C32 b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
-    C32 b4 = cadd(a4, a6), b6 = mul_mi(csub(a4, a6));
-    C32 t5 = cadd(a5, a7), t7 = csub(a5, a7);
-    C32 b5 = {(t5.x + t5.y) * s, (t5.y - t5.x) * s};          // * e^{-i pi/4}
-    C32 b7 = {(t7.y - t7.x) * s, (-t7.x - t7.y) * s};         // * e^{-3i pi/4}
-    v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
-    v[1] = cadd(b1, b5); v[5] = csub(b1, b5);
-    v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
-    v[3] = cadd(b3, b7); v[7] = csub(b3, b7);
-}
 
 struct LogmelArgs {
     const float* wave; float* out;
@@ -79,7 +55,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
     for (int s = 0; s < FPB / 4; ++s) {
         const int f = w + 4 * s;
         const int t = min(t0 + f, a.T - 1);          // clamped duplicate keeps barriers uniform
-        C32 v[8];
+        v2 v[8];
         // ---- pass 0 (Ns = 1): inputs z[m] = x[2m] + i x[2m+1], m = lane + 64 r
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
@@ -90,7 +66,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
             v[r].x = x[p0] * a.win[n];
             v[r].y = x[p1] * a.win[n + 1];
         }
-        dft8(v);
+        dft8v(v);
 #pragma unroll
         for (int r = 0; r < 8; ++r) { const int o = pidx(8 * lane + r); re[o] = v[r].x; im[o] = v[r].y; }
         __syncthreads();
@@ -100,11 +76,11 @@ __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const int o = pidx(lane + 64 * r);
-                C32 z = {re[o], im[o]};
+                const v2 z = v2{re[o], im[o]};
                 const int ti = 16 * r * k;
-                v[r] = cmul(z, C32{s_tw[2 * ti], s_tw[2 * ti + 1]});
+                v[r] = cmulv(z, v2{s_tw[2 * ti], s_tw[2 * ti + 1]});
             }
-            dft8(v);
+            dft8v(v);
             __syncthreads();
             const int j0 = (lane >> 3) * 64 + (lane & 7);
 #pragma unroll
@@ -116,11 +92,11 @@ __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const int o = pidx(lane + 64 * r);
-                C32 z = {re[o], im[o]};
+                const v2 z = v2{re[o], im[o]};
                 const int ti = 2 * r * lane;
-                v[r] = cmul(z, C32{s_tw[2 * ti], s_tw[2 * ti + 1]});
+                v[r] = cmulv(z, v2{s_tw[2 * ti], s_tw[2 * ti + 1]});
             }
-            dft8(v);
+            dft8v(v);
             __syncthreads();
 #pragma unroll
             for (int r = 0; r < 8; ++r) { const int o = pidx(lane + 64 * r); re[o] = v[r].x; im[o] = v[r].y; }
@@ -131,12 +107,10 @@ __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
         for (int r = 0; r < 8; ++r) {
             const int k = lane + 64 * r;
             const int o2 = pidx((512 - k) & 511);
-            const C32 A = v[r];
-            const C32 Bc = {re[o2], -im[o2]};
-            const C32 E = {0.5f * (A.x + Bc.x), 0.5f * (A.y + Bc.y)};
-            const C32 O = {0.5f * (A.x - Bc.x), 0.5f * (A.y - Bc.y)};
-            const C32 WO = cmul(C32{s_tw[2 * k], s_tw[2 * k + 1]}, O);
-            const C32 X = {E.x + WO.y, E.y - WO.x};                 // E - i*WO
+            const v2 A = v[r], Bc = v2{re[o2], -im[o2]};
+            const v2 E = (A + Bc) * 0.5f, O = (A - Bc) * 0.5f;
+            const v2 WO = cmulv(v2{s_tw[2 * k], s_tw[2 * k + 1]}, O);
+            const v2 X = v2{E.x + WO.y, E.y - WO.x};                // E - i*WO
             pw[k] = X.x * X.x + X.y * X.y + a.eps_pow;
             if (k == 0) { const float ny = A.x - A.y; pw[512] = ny * ny + a.eps_pow; }
         }
@@ -162,40 +136,17 @@ __global__ __launch_bounds__(256) void logmel_kernel(LogmelArgs a) {
 // Second form: one PERSISTENT wave per run of frames, nothing but the samples and the results crosses HBM more than once.
 // The kernel above is bound by its LDS traffic and scalar fp32 issue, not by memory (3 % of the HBM roof): every frame fetched
 // 12 KB of twiddles and up to 23 KB of padded mel rows from LDS, its window from global memory, and used one fp32 lane-op per
-// real multiply-add.  Here
+// real multiply-add.  Here, on the wave-level FFT of wave_fft.h,
 //   * window, the three twiddle sets and the wave's mel rows live in registers for the whole launch (a lane is a mel row);
-//   * complex values travel as float2 (packed fp32 math, 8-byte LDS accesses); the conjugate-mirror operand of the real-FFT
-//     split comes from ds_bpermute instead of a third LDS exchange; no workgroup barrier anywhere (waves are independent);
+//   * the conjugate-mirror operand of the real-FFT split comes from ds_bpermute instead of a third LDS exchange; no workgroup
+//     barrier anywhere (waves are independent);
 //   * the mel row is read as 16-byte aligned LDS chunks against register weights (13 ds_read_b128 instead of 90 ds_read_b32);
 //   * interior frames load their 1,024 samples as eight coalesced float2 per lane (no reflect arithmetic).
-typedef float v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2 cmulv(v2 a, v2 b) { return v2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ v2 mulmi(v2 a) { return v2{a.y, -a.x}; }     // * (-i)
-__device__ __forceinline__ void dft8v(v2* v) {
-    const float s = 0.70710678118654752440f;
-    v2 a0 = v[0] + v[4], a1 = v[0] - v[4];
-    v2 a2 = v[2] + v[6], a3 = mulmi(v[2] - v[6]);
-    v2 a4 = v[1] + v[5], a5 = v[1] - v[5];
-    v2 a6 = v[3] + v[7], a7 = mulmi(v[3] - v[7]);
-    v2 b0 = a0 + a2, b2 = a0 - a2, b1 = a1 + a3, b3 = a1 - a3;
-    v2 b4 = a4 + a6, b6 = mulmi(a4 - a6);
-    v2 t5 = a5 + a7, t7 = a5 - a7;
-    v2 b5 = v2{(t5.x + t5.y) * s, (t5.y - t5.x) * s};          // * e^{-i pi/4}
-    v2 b7 = v2{(t7.y - t7.x) * s, (-t7.x - t7.y) * s};         // * e^{-3i pi/4}
-    v[0] = b0 + b4; v[4] = b0 - b4;
-    v[1] = b1 + b5; v[5] = b1 - b5;
-    v[2] = b2 + b6; v[6] = b2 - b6;
-    v[3] = b3 + b7; v[7] = b3 - b7;
-}
-__device__ __forceinline__ void wave_fence() { asm volatile("" ::: "memory"); }     // LDS is in-order per wave: only the compiler must not reorder
-
-constexpr int EXW = 576;                // float2 exchange buffer of a wave (512 + 512 / 8 padding)
 constexpr int PWW = 576;                // floats: 513 power bins + zero tail up to the last aligned mel chunk
-// Output staging: a wave collects up to OTF consecutive frames of its run in an LDS tile [mel row][frame] and writes them out as
-// row segments of up to OTF * 4 = 128 contiguous bytes (32 lanes per mel row, 2 rows per store instruction).  Storing each frame on its
-// own - one float per lane, lane = mel row, 4 * T bytes apart - made every store instruction 64 partial-line writes: 140 MB left
-// the L2 per launch for 13.2 MB of output (PMC WRITE_SIZE, round 2).
-constexpr int OTF = 32, OTP = OTF + 1;  // frames per tile; row pitch in floats (odd: the per-frame column writes are conflict-free)
+// Output staging (wave_tile_flush): up to OTF consecutive frames of a wave's run leave as row segments of up to OTF * 4 = 128
+// contiguous bytes.  Storing each frame on its own made every store instruction 64 partial-line writes: 140 MB left the L2 per
+// launch for 13.2 MB of output (PMC WRITE_SIZE, round 2).
+constexpr int OTF = 32, OTP = OTF + 1;  // frames per tile; row pitch in floats
 // (OTF = 16: 64-byte segments at the 404-byte row pitch of T = 101 straddle three 32-byte sectors - 23.1 MB left the L2 for 13.2 MB
 // of output; at B = 512 a wave's run is 25-26 frames of one clip, so 32 columns give ONE flush of ~100-byte segments per run)
 
@@ -214,31 +165,16 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
     for (int i = 513 + lane; i < PWW; i += 64) pw[i] = 0.f;
 
     // ---- per-lane constants
-    v2 win[8], tw1[8], tw2[8], tws[8];
-    const v2* twt = reinterpret_cast<const v2*>(a.tw);
+    v2 win[8], tw1[8], tw2[8], tws[8];                       // tws: W_1024^k of the real-FFT split
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int n = 2 * (lane + 64 * r);
         win[r] = v2{a.win[n], a.win[n + 1]};
-        tw1[r] = twt[16 * r * (lane & 7)];
-        tw2[r] = twt[2 * r * lane];
-        tws[r] = twt[lane + 64 * r];
+        tws[r] = reinterpret_cast<const v2*>(a.tw)[lane + 64 * r];
     }
-    float mw[MPL][4 * NCH];
-    int ma[MPL];
-#pragma unroll
-    for (int q = 0; q < MPL; ++q) {
-        const int m = lane + 64 * q;
-        const int st = m < a.n_mels ? a.mel_start[m] : 0;
-        ma[q] = st & ~3;
-#pragma unroll
-        for (int j = 0; j < 4 * NCH; ++j) {
-            const int i = ma[q] + j - st;
-            mw[q][j] = (m < a.n_mels && i >= 0 && i < a.taps) ? a.melw[m * a.taps + i] : 0.f;
-        }
-    }
-    const int mirror = ((64 - lane) & 63) * 4;               // ds_bpermute source lane (bytes)
-    const int j0 = (lane >> 3) * 64 + (lane & 7);
+    wave_fft_twiddles<2>(a.tw, lane, tw1, tw2);
+    MelRows<MPL, NCH> mel;
+    mel.load(a.melw, a.mel_start, a.n_mels, a.taps, NFFT / 2, lane);
 
     // frame range of this wave - wave-uniform values kept in scalar registers (readfirstlane), so the frame loop, the
     // clip / frame split and the interior-or-border choice are scalar code
@@ -306,36 +242,11 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = nxt[r] * win[r];
         if (f + 1 < f1) { cn = step(cur, f + 1); load_frame(cn, nxt); }   // the next frame's samples travel while this frame is transformed
-        // ---- pass 0 (Ns = 1)
-        dft8v(v);
-        wave_fence();
-#pragma unroll
-        for (int r = 0; r < 8; ++r) ex[pidx(8 * lane + r)] = v[r];
-        wave_fence();
-        // ---- pass 1 (Ns = 8)
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = ex[pidx(lane + 64 * r)];
-#pragma unroll
-        for (int r = 1; r < 8; ++r) v[r] = cmulv(v[r], tw1[r]);
-        dft8v(v);
-        wave_fence();
-#pragma unroll
-        for (int r = 0; r < 8; ++r) ex[pidx(j0 + 8 * r)] = v[r];
-        wave_fence();
-        // ---- pass 2 (Ns = 64): Z[lane + 64 r]
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = ex[pidx(lane + 64 * r)];
-#pragma unroll
-        for (int r = 1; r < 8; ++r) v[r] = cmulv(v[r], tw2[r]);
-        dft8v(v);
-        // ---- real-FFT split; Z[512 - k] sits in lane 64 - lane, register 7 - r (lane 0: its own register 8 - r)
+        wave_fft512(v, ex, lane, tw1, tw2);
+        // ---- real-FFT split: X[k] = E - i W_1024^k O,  E = (Z[k] + conj Z[512-k])/2, O = (Z[k] - conj Z[512-k])/2
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const v2 own = v[(8 - r) & 7], oth = v[7 - r];
-            v2 zm;
-            zm.x = __int_as_float(__builtin_amdgcn_ds_bpermute(mirror, __float_as_int(oth.x)));
-            zm.y = __int_as_float(__builtin_amdgcn_ds_bpermute(mirror, __float_as_int(oth.y)));
-            if (lane == 0) zm = own;
+            const v2 zm = wave_fft_mirror(v, r, lane);
             const v2 A = v[r], Bc = v2{zm.x, -zm.y};
             const v2 E = (A + Bc) * 0.5f, O = (A - Bc) * 0.5f;
             const v2 WO = cmulv(tws[r], O);
@@ -347,27 +258,15 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
         // ---- mel rows: aligned 16-byte chunks of the power spectrum against register weights, then log
 #pragma unroll
         for (int q = 0; q < MPL; ++q) {
-            float acc = 0.f;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const f32x4 p = *reinterpret_cast<const f32x4*>(pw + ma[q] + 4 * c);
-                acc += mw[q][4 * c] * p[0] + mw[q][4 * c + 1] * p[1] + mw[q][4 * c + 2] * p[2] + mw[q][4 * c + 3] * p[3];
-            }
-            ot[(lane + 64 * q) * OTP + tl] = a.apply_log ? logf(acc + a.eps_log) : acc;
+            float acc[1];
+            mel.dot(q, {pw}, acc);
+            ot[(lane + 64 * q) * OTP + tl] = a.apply_log ? logf(acc[0] + a.eps_log) : acc[0];
         }
         wave_fence();
         // ---- flush the tile when it is full, at the end of a clip (the next frame belongs to another clip's rows) and at the
-        //      end of the run: frames t - tl .. t of clip b, OTF lanes per mel row
+        //      end of the run: frames t - tl .. t of clip b
         if (tl == OTF - 1 || t == cur.Tb - 1 || f == f1 - 1) {
-            const int col = lane & (OTF - 1), t0 = t - tl;
-            float* const dst = a.out + (long)b * a.n_mels * a.T + t0 + col;
-            constexpr int RPI = 64 / OTF;                    // mel rows per store instruction
-#pragma unroll 4
-            for (int i = 0; i < 64 * MPL / RPI; ++i) {
-                const int row = RPI * i + lane / OTF;
-                const float v = ot[row * OTP + col];
-                if (col <= tl && row < a.n_mels) dst[(long)row * a.T] = v;
-            }
+            wave_tile_flush<OTF, 64 * MPL>(ot, a.out + (long)b * a.n_mels * a.T + t - tl, tl + 1, a.n_mels, a.T, lane);
             if constexpr (RAGGED) {
                 if (t == cur.Tb - 1) {                       // the clip is done: zeros over its tail frames, row by row
                     float* const z0 = a.out + (long)b * a.n_mels * a.T;
@@ -381,6 +280,25 @@ __global__ __launch_bounds__(256) void logmel2_kernel(LogmelArgs a, int total_fr
             ++tl;
         }
     }
+}
+
+// Does the packed bank fit the persistent kernel's registers: a row and its alignment slack in 13 chunks of 4 bins at one mel
+// row per lane, in 7 at two.
+bool persistent_fits(int n_mels, int taps) { return n_mels <= 64 ? taps + 3 <= 4 * 13 : taps + 3 <= 4 * 7; }
+
+// The persistent kernel over `total` frames, in the form persistent_fits chose.
+template <bool RAGGED>
+int launch_persistent(const LogmelArgs& a, long total, hipStream_t s) {
+    const int blocks = (int)min((long)512, (total + 3) / 4);              // two workgroups per CU, ~25 frames per wave at B = 512
+    const size_t lds = sizeof(float) * 4 * (2 * EXW + PWW + 64 * (a.n_mels <= 64 ? 1 : 2) * OTP);
+    if (a.n_mels <= 64) {
+        g_assl_last_kernel = RAGGED ? "logmel2_kernel<1, 13, true>" : "logmel2_kernel<1, 13, false>";
+        hipLaunchKernelGGL((logmel2_kernel<1, 13, RAGGED>), dim3(blocks), dim3(256), lds, s, a, (int)total);
+    } else {
+        g_assl_last_kernel = RAGGED ? "logmel2_kernel<2, 7, true>" : "logmel2_kernel<2, 7, false>";
+        hipLaunchKernelGGL((logmel2_kernel<2, 7, RAGGED>), dim3(blocks), dim3(256), lds, s, a, (int)total);
+    }
+    ASSL_LAUNCH_CHECK();
 }
 
 }  // namespace
@@ -398,14 +316,8 @@ extern "C" int audiossl_logmel_fwd(const float* wave, float* out, int B, int L, 
     // the persistent form needs 8-byte aligned frame starts and mel rows that fit its register budget
     static const int v1_only = getenv("AUDIOSSL_LOGMEL_V1") ? atoi(getenv("AUDIOSSL_LOGMEL_V1")) : 0;
     const bool v2_ok = !v1_only && hop % 2 == 0 && L % 2 == 0 && (((uintptr_t)wave) & 7) == 0 && L >= NFFT;
-    if (v2_ok && (n_mels <= 64 ? taps + 3 <= 52 : taps + 3 <= 28)) {
-        const long total = (long)B * T;
-        const int blocks = (int)min((long)512, (total + 3) / 4);          // two workgroups per CU, ~25 frames per wave at B = 512
-        const size_t lds = sizeof(float) * 4 * (2 * EXW + PWW + 64 * (n_mels <= 64 ? 1 : 2) * OTP);
-        if (n_mels <= 64) hipLaunchKernelGGL((logmel2_kernel<1, 13, false>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
-        else              hipLaunchKernelGGL((logmel2_kernel<2, 7, false>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
-        ASSL_LAUNCH_CHECK();
-    }
+    if (v2_ok && persistent_fits(n_mels, taps)) return launch_persistent<false>(a, (long)B * T, static_cast<hipStream_t>(stream));
+    g_assl_last_kernel = "logmel_kernel";
     hipLaunchKernelGGL(logmel_kernel, dim3(ceil_div(T, FPB), B), dim3(256), dyn, static_cast<hipStream_t>(stream), a);
     ASSL_LAUNCH_CHECK();
 }
@@ -419,7 +331,7 @@ extern "C" int audiossl_logmel_ragged_fwd(const float* wave, const int* lens, co
     ASSL_REQUIRE(wave && lens && lens_host && out && win && tw && melw && mel_start);
     ASSL_REQUIRE(n_fft == NFFT);
     ASSL_REQUIRE(B > 0 && hop > 0 && hop % 2 == 0 && Lmax > 0 && Lmax % 2 == 0 && Tmax > 0 && n_mels > 0 && n_mels <= 128 && taps > 0);
-    ASSL_REQUIRE(n_mels <= 64 ? taps + 3 <= 52 : taps + 3 <= 28);          // the mel rows fit the kernel's registers
+    ASSL_REQUIRE(persistent_fits(n_mels, taps));
     constexpr int MIN_LEN = 1120;      // 8 frames at hop 160: one row after three pools; > n_fft / 2, so a reflection stays inside the clip
     long total = 0;
     int longest = 0;
@@ -432,9 +344,5 @@ extern "C" int audiossl_logmel_ragged_fwd(const float* wave, const int* lens, co
     ASSL_REQUIRE(Tmax >= 1 + longest / hop && total < (1l << 31) && (long)B * Tmax < (1l << 31));
     if ((((uintptr_t)wave) & 7) != 0) return ASSL_EALIGN;                  // interior frames are read as float2
     LogmelArgs a{wave, out, B, Lmax, Tmax, hop, n_mels, taps, win, tw, melw, mel_start, eps_pow, eps_log, apply_log, lens};
-    const int blocks = (int)min((long)512, (total + 3) / 4);
-    const size_t lds = sizeof(float) * 4 * (2 * EXW + PWW + 64 * (n_mels <= 64 ? 1 : 2) * OTP);
-    if (n_mels <= 64) hipLaunchKernelGGL((logmel2_kernel<1, 13, true>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
-    else              hipLaunchKernelGGL((logmel2_kernel<2, 7, true>), dim3(blocks), dim3(256), lds, static_cast<hipStream_t>(stream), a, (int)total);
-    ASSL_LAUNCH_CHECK();
+    return launch_persistent<true>(a, total, static_cast<hipStream_t>(stream));
 }
