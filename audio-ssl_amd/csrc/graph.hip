@@ -11,10 +11,9 @@
 //   j ascending).  Self is excluded by INDEX, so a duplicate row is a legitimate neighbour at distance 0.  Few rows: the
 //   walked rows are split over blockIdx.y, every split writes its k best to the workspace, topk_merge_kernel folds them.
 //
-// pic_build: CSR of W = A + A^T, A_ij = exp(-d2_ij / sigma^2) for j in row i's list (fp64 from the fp32 distance): count
-//   in-degrees (integer atomics), scan, scatter (out-edges at fixed slots, in-edges through an integer cursor), then each
-//   row is sorted by column (rank sort: any in-degree up to n - 1 works) and a mutual pair merged into one entry
-//   a_ij + a_ji - two terms, so the order in which the cursor handed out slots does not reach the result.
+// pic_build: CSR of W = A + A^T, A_ij = exp(-d2_ij / sigma^2) for j in row i's list (fp64 from the fp32 distance), by the
+//   builder of csr_sym.h (shared with tsne.hip): columns ascending in every row, a mutual pair merged into one entry
+//   a_ij + a_ji.
 // pic_power: v = 1/n; iters x { u = alpha W v + (1 - alpha) / n; v = u / sum(u) }: a row's sum in column order by one
 //   thread, the global sum in a fixed tree (per-workgroup partials, folded the same way by every workgroup).
 // pic_assign: parent(i) = argmax_j W_ij (v_j - v_i) over strictly positive values, ties to the smaller j, else i
@@ -24,6 +23,7 @@
 // No float atomics, no grid-wide barriers, plain launches only; the kernels initialise whatever they read of the workspace.
 #include "topk.h"
 #include "gram_tile.h"
+#include "csr_sym.h"
 
 namespace {
 
@@ -101,113 +101,6 @@ bool graph_plan(int n, int k, GraphPlan& p) {
 
 // ---- PIC ------------------------------------------------------------------------------------------------------------------
 
-// out[i] = sum over t < i of (in[t] + add), out[n] = the total (also to *total when given).  One workgroup: every thread
-// sums a contiguous run, the 1024 run sums are scanned in LDS.
-__global__ __launch_bounds__(1024) void pic_scan_kernel(const int* __restrict__ in, int add, int n, int* __restrict__ out,
-                                                        int* __restrict__ total) {
-    __shared__ int sh[1024];
-    const int tid = threadIdx.x;
-    const long chunk = ((long)n + 1023) / 1024;
-    const long lo = min(tid * chunk, (long)n), hi = min(lo + chunk, (long)n);
-    int s = 0;
-    for (long i = lo; i < hi; ++i) s += in[i] + add;
-    sh[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int t = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    int base = sh[tid] - s;
-    for (long i = lo; i < hi; ++i) { out[i] = base; base += in[i] + add; }
-    if (tid == 1023) {
-        out[n] = sh[1023];
-        if (total) total[0] = sh[1023];
-    }
-}
-
-__global__ __launch_bounds__(256) void pic_count_kernel(const int* __restrict__ idx, long edges, int n, int* __restrict__ cnt) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= edges) return;
-    const int j = idx[e];
-    if (j >= 0 && j < n) atomicAdd(&cnt[j], 1);
-}
-
-// Row i of the unsorted graph: slots 0..k-1 its own list (an index outside [0, n) leaves an INT_MAX column that the merge
-// drops), then one slot per in-edge in cursor order.
-__global__ __launch_bounds__(256) void pic_scatter_kernel(const int* __restrict__ idx, const float* __restrict__ d2, long edges, int n,
-                                                          int k, double sigma2, const int* __restrict__ ptr, int* __restrict__ fill,
-                                                          int* __restrict__ raw_col, double* __restrict__ raw_w) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= edges) return;
-    const int i = (int)(e / k), t = (int)(e % k);
-    const int j = idx[e];
-    const bool ok = j >= 0 && j < n;
-    const double aij = exp(-(double)d2[e] / sigma2);
-    const long o = (long)ptr[i] + t;
-    raw_col[o] = ok ? j : INT_MAX;
-    raw_w[o] = ok ? aij : 0.;
-    if (ok) {
-        const long pos = (long)ptr[j] + k + atomicAdd(&fill[j], 1);
-        raw_col[pos] = i;
-        raw_w[pos] = aij;
-    }
-}
-
-// One wave per row: rank sort by (column, slot) - a row may be as long as k + n - 1 (a hub that is in every list).
-__global__ __launch_bounds__(256) void pic_sort_kernel(const int* __restrict__ ptr, int n, const int* __restrict__ raw_col,
-                                                       const double* __restrict__ raw_w, int* __restrict__ srt_col,
-                                                       double* __restrict__ srt_w) {
-    const int lane = threadIdx.x & 63;
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const long base = ptr[i];
-    const int len = ptr[i + 1] - ptr[i];
-    for (int e = lane; e < len; e += 64) {
-        const int c = raw_col[base + e];
-        int rank = 0;
-        for (int f = 0; f < len; ++f) {
-            const int cf = raw_col[base + f];
-            rank += (cf < c || (cf == c && f < e)) ? 1 : 0;
-        }
-        srt_col[base + rank] = c;
-        srt_w[base + rank] = raw_w[base + e];
-    }
-}
-
-// One wave per sorted row: the first entry of every run of equal columns is a head.  WRITE = false counts the heads,
-// WRITE = true writes head columns and the run's sum (a mutual pair: two terms) at rowptr[i].
-template <bool WRITE>
-__global__ __launch_bounds__(256) void pic_merge_kernel(const int* __restrict__ ptr, int n, const int* __restrict__ srt_col,
-                                                        const double* __restrict__ srt_w, int* __restrict__ ucnt,
-                                                        const int* __restrict__ rowptr, int* __restrict__ col,
-                                                        double* __restrict__ w) {
-    const int lane = threadIdx.x & 63;
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const long base = ptr[i];
-    const int len = ptr[i + 1] - ptr[i];
-    int run = 0;
-    for (int p0 = 0; p0 < len; p0 += 64) {
-        const int p = p0 + lane;
-        const bool in = p < len;
-        const int c = in ? srt_col[base + p] : INT_MAX;
-        const int prev = (in && p > 0) ? srt_col[base + p - 1] : -1;
-        const bool head = in && c != INT_MAX && c != prev;
-        const unsigned long long m = __ballot(head);
-        if (WRITE && head) {
-            double s = srt_w[base + p];
-            for (int f = p + 1; f < len && srt_col[base + f] == c; ++f) s += srt_w[base + f];
-            const long o = (long)rowptr[i] + run + __popcll(m & ((1ull << lane) - 1ull));
-            col[o] = c;
-            w[o] = s;
-        }
-        run += __popcll(m);
-    }
-    if (!WRITE && lane == 0) ucnt[i] = run;
-}
-
 __global__ __launch_bounds__(256) void pic_fill_kernel(double* __restrict__ v, int n, double value) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) v[i] = value;
@@ -279,11 +172,16 @@ __global__ __launch_bounds__(256) void pic_label_kernel(const int* __restrict__ 
     if (i < n) label[i] = cid[root[i]];
 }
 
-long align16(long b) { return (b + 15) / 16 * 16; }
+// A_ij of edge e = i k + t, in fp64 from the fp32 distance.
+struct PicWeight {
+    const float* d2;
+    double sigma2;
+    __device__ double operator()(long e) const { return exp(-(double)d2[e] / sigma2); }
+};
 
 struct PicPlan {
-    long edges, cap;
-    long off_raw_w, off_srt_w, off_raw_col, off_srt_col, off_cnt, off_fill, off_ptr, off_ucnt, build_bytes;
+    CsrSymPlan build;
+    long build_bytes;
     long off_u, off_part, power_bytes;
     long off_pa, off_pb, off_flag, off_cid, assign_bytes;
     long bytes;
@@ -291,29 +189,18 @@ struct PicPlan {
 };
 
 bool pic_plan(int n, int k, PicPlan& p) {
-    if (!(n >= 2 && k >= 1 && k <= n - 1 && (long)n * k < (1L << 30))) return false;
-    p.edges = (long)n * k;
-    p.cap = 2 * p.edges;
-    long o = 0;
-    p.off_raw_w = o;   o += p.cap * 8;
-    p.off_srt_w = o;   o += p.cap * 8;
-    p.off_raw_col = o; o += align16(p.cap * 4);
-    p.off_srt_col = o; o += align16(p.cap * 4);
-    p.off_cnt = o;     o += align16((long)n * 4);
-    p.off_fill = o;    o += align16((long)n * 4);            // directly behind cnt: one clear serves both
-    p.off_ptr = o;     o += align16(((long)n + 1) * 4);
-    p.off_ucnt = o;    o += align16((long)n * 4);
-    p.build_bytes = o;
+    if (!csr_sym_plan(n, k, p.build)) return false;
+    p.build_bytes = p.build.bytes;
     p.nparts = (int)(((long)n + 255) / 256);
-    o = 0;
+    long o = 0;
     p.off_u = o;       o += (long)n * 8;
     p.off_part = o;    o += (long)p.nparts * 8;
-    p.power_bytes = align16(o);
+    p.power_bytes = csr_align16(o);
     o = 0;
-    p.off_pa = o;      o += align16((long)n * 4);
-    p.off_pb = o;      o += align16((long)n * 4);
-    p.off_flag = o;    o += align16((long)n * 4);
-    p.off_cid = o;     o += align16(((long)n + 1) * 4);
+    p.off_pa = o;      o += csr_align16((long)n * 4);
+    p.off_pb = o;      o += csr_align16((long)n * 4);
+    p.off_flag = o;    o += csr_align16((long)n * 4);
+    p.off_cid = o;     o += csr_align16(((long)n + 1) * 4);
     p.assign_bytes = o;
     p.bytes = p.build_bytes > p.power_bytes ? p.build_bytes : p.power_bytes;
     if (p.assign_bytes > p.bytes) p.bytes = p.assign_bytes;
@@ -377,27 +264,7 @@ extern "C" int audiossl_pic_build(const int* idx, const float* d2, int n, int k,
     ASSL_REQUIRE(workspace_bytes >= p.build_bytes);
     if (!ASSL_ALIGNED16(workspace)) return ASSL_EALIGN;
     hipStream_t s = S_(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* raw_w = reinterpret_cast<double*>(ws + p.off_raw_w);
-    double* srt_w = reinterpret_cast<double*>(ws + p.off_srt_w);
-    int* raw_col = reinterpret_cast<int*>(ws + p.off_raw_col);
-    int* srt_col = reinterpret_cast<int*>(ws + p.off_srt_col);
-    int* cnt = reinterpret_cast<int*>(ws + p.off_cnt);
-    int* fill = reinterpret_cast<int*>(ws + p.off_fill);
-    int* ptr = reinterpret_cast<int*>(ws + p.off_ptr);
-    int* ucnt = reinterpret_cast<int*>(ws + p.off_ucnt);
-    const dim3 rows4((unsigned)(((long)n + 3) / 4));
-    ASSL_ZERO_ALWAYS(cnt, (size_t)(p.off_ptr - p.off_cnt), s);                   // cnt and fill are adjacent
-    hipLaunchKernelGGL(pic_count_kernel, GRID1(p.edges), dim3(256), 0, s, idx, p.edges, n, cnt);
-    hipLaunchKernelGGL(pic_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, k, n, ptr, static_cast<int*>(nullptr));
-    hipLaunchKernelGGL(pic_scatter_kernel, GRID1(p.edges), dim3(256), 0, s, idx, d2, p.edges, n, k, sigma * sigma, ptr, fill, raw_col,
-                       raw_w);
-    hipLaunchKernelGGL(pic_sort_kernel, rows4, dim3(256), 0, s, ptr, n, raw_col, raw_w, srt_col, srt_w);
-    hipLaunchKernelGGL(pic_merge_kernel<false>, rows4, dim3(256), 0, s, ptr, n, srt_col, srt_w, ucnt, static_cast<const int*>(nullptr),
-                       static_cast<int*>(nullptr), static_cast<double*>(nullptr));
-    hipLaunchKernelGGL(pic_scan_kernel, dim3(1), dim3(1024), 0, s, ucnt, 0, n, rowptr, nnz);
-    hipLaunchKernelGGL(pic_merge_kernel<true>, rows4, dim3(256), 0, s, ptr, n, srt_col, srt_w, static_cast<int*>(nullptr), rowptr, col, w);
-    ASSL_LAUNCH_CHECK();
+    return csr_sym_build<double>(p.build, idx, n, k, PicWeight{d2, sigma * sigma}, 1.0, rowptr, col, w, nnz, workspace, s);
 }
 
 extern "C" int audiossl_pic_power(const int* rowptr, const int* col, const double* w, int n, long cap, double alpha, int iters,
@@ -443,7 +310,7 @@ extern "C" int audiossl_pic_assign(const int* rowptr, const int* col, const doub
         int* t = pa; pa = pb; pb = t;
     }
     hipLaunchKernelGGL(pic_root_flag_kernel, GRID1(n), dim3(256), 0, s, pa, n, flag);
-    hipLaunchKernelGGL(pic_scan_kernel, dim3(1), dim3(1024), 0, s, flag, 0, n, cid, count);
+    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, s, flag, 0, n, cid, count);
     hipLaunchKernelGGL(pic_label_kernel, GRID1(n), dim3(256), 0, s, pa, cid, n, label);
     ASSL_LAUNCH_CHECK();
 }

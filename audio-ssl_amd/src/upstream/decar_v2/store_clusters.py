@@ -8,6 +8,8 @@ PCA-whiten, cluster, and write the `files,label` CSV `train_upstream.py --upstre
         --clustering pic --score --out labelled.csv
     python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv \
         --k_sweep 64,128,256 --out labelled.csv
+    python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv --k 585 \
+        --out labelled.csv --map map.csv
 
 `--clustering kmeans` (the default) needs `--k`.  `--clustering pic` is the reference's other algorithm (`PIC`, imported next to
 `Kmeans` at `store_clusters.py:18`): power-iteration clustering on an exact nearest-neighbour graph, which finds the number of
@@ -19,6 +21,9 @@ features they were computed on: the label-free answer to "is this labeling any g
 all pairs on the GPU, no distance matrix stored).  `--k_sweep 64,128,256` takes the place of `--k`: the files are embedded and
 whitened once, k-means runs for every k in the order given, one line per k reports its silhouette, and the labeling with the
 highest silhouette (a tie: the smaller k) is written; the reference has neither.
+`--map map.csv` draws the picture that goes with the numbers: a 2-D t-SNE layout (`src.evaluation.tsne.tsne`, exact repulsion on
+the GPU, `--perplexity` up to 21, `--map_iters` iterations) of the same whitened features, written as `files,label,x,y` for any
+plotting tool to colour by label; one more line reports the final KL divergence.
 `--window random` is the default: the reference draws `extract_window` for every clip; `--window whole` embeds every clip at its
 own length (up to `--max_duration` seconds).  Single GPU.
 """
@@ -80,6 +85,9 @@ def main(args):
         with open(args.config, "r") as f:
             config = yaml.load(f, Loader=yaml.SafeLoader)
     files = list(pd.read_csv(args.input)["files"])
+    if args.map:
+        from src.evaluation.tsne import neighbour_count
+        neighbour_count(len(files), args.perplexity)                     # a perplexity the map cannot have: refused before the embedding
     embedder = load_embedder(args.checkpoint, args.upstream, config=config, layer=args.layer)
     duration = float(embedder.model.config["pretrain"]["input"]["length_wave"])
     feats = extract_embeddings(embedder, files, batch_size=args.batch_size, window=args.window, duration=duration,
@@ -104,6 +112,12 @@ def main(args):
     if args.score:
         score, count, singles = _silhouette(model.features, labels)
         print(f"silhouette {_fmt(score)} ({count} clusters, {singles} singletons)")
+    if args.map:
+        from src.evaluation.tsne import tsne
+        y, kl = tsne(model.features, perplexity=args.perplexity, n_iter=args.map_iters, return_kl=True)
+        y = y.cpu().numpy()
+        pd.DataFrame({"files": files, "label": [int(c) for c in labels], "x": y[:, 0], "y": y[:, 1]}).to_csv(args.map, index=False)
+        print(f"map of {len(files)} files, perplexity {args.perplexity:g}, {args.map_iters} iterations, KL {kl:.6f} -> {args.map}")
     if args.compare:
         from src.evaluation.graph import partition_nmi
         other = pd.read_csv(args.compare)
@@ -143,6 +157,9 @@ def get_args(argv=None):
     parser.add_argument("--no_distribute_singletons", action="store_true", help="pic: keep one-member clusters")
     parser.add_argument("--compare", type=str, default=None, help="another `files,label` csv: print the NMI against it")
     parser.add_argument("--score", action="store_true", help="print the silhouette coefficient of the labels just written")
+    parser.add_argument("--map", type=str, default=None, help="`files,label,x,y` csv to write: a 2-D t-SNE map of the whitened features")
+    parser.add_argument("--perplexity", type=float, default=20.0, help="--map: t-SNE perplexity, 1 .. 21")
+    parser.add_argument("--map_iters", type=int, default=1000, help="--map: t-SNE iterations")
     parser.add_argument("--window", choices=("center", "random", "whole"), default="random",
                         help="whole: every clip at its own length, in ragged batches (conv encoder)")
     parser.add_argument("--max_duration", type=float, default=30.0, help="--window whole: longer clips are centre-cropped to this many seconds")

@@ -584,6 +584,43 @@ int audiossl_silhouette_workspace(int n, long* bytes);
 int audiossl_silhouette(const float* xs, int n, int d, const int* seg, const int* seg_host, int K, double* s, void* workspace,
                         long workspace_bytes, void* stream);
 
+/* ---- t-SNE map of a feature matrix (csrc/tsne.hip): van der Maaten & Hinton 2008 with the parameters and schedule of
+ * `sklearn.manifold.TSNE`: sparse affinities on each point's nearest neighbours (its `barnes_hut` path), EXACT repulsion (what
+ * `angle = 0` would give); the reference has no counterpart.  Nothing holds n x n numbers; no float atomics: two calls on the same
+ * inputs agree bit for bit; every workspace is device memory that needs no clearing; nothing synchronises with the host.
+ * Every entry returns EINVAL for a null pointer, n < 2 or k outside [1, 64] before any launch.
+ * tsne_calibrate: d2 [n][k] fp32 as knn_graph_l2 wrote it -> p_cond [n][k] fp32, p_j|i = exp(-beta_i (d2_ij - min_t d2_it)) / sum,
+ *   and beta [n] fp32.  beta_i by the bisection of `_binary_search_perplexity` (sklearn/manifold/_utils.pyx): from 1, doubled or
+ *   halved while a bound is infinite, then the midpoint, at most 100 steps, until |H_i - log(perplexity)| <= 1e-5 with
+ *   H_i = -sum_j p_j|i log p_j|i of the row as it is stored (fp32), so the stored row meets the tolerance itself; search,
+ *   exponentials, logs and sums in fp64.  A row of equal distances ends as the uniform
+ *   row 1 / k.  0 < perplexity <= k, k <= n - 1, n k < 2^30; distances finite.
+ * tsne_symmetrize: idx [n][k] int32 (a row's entries distinct, no self; an index outside [0, n) is dropped), p_cond [n][k] ->
+ *   CSR of P = (P_cond + P_cond^T) / (2 n): rowptr [n + 1] int32, col int32 and p fp32 [2 n k] (capacity; nnz[0] entries are
+ *   written), columns ascending in every row, a mutual pair merged into one entry (the two terms added in fp64, rounded once).
+ * tsne_repulsion: y [n][2] fp32 -> rep [n][2] fp32, rep_i = sum_{j != i} w_ij^2 (y_i - y_j), and Z[0] (device, fp64) =
+ *   sum_{i != j} w_ij with w_ij = 1 / (1 + |y_i - y_j|^2).  All n (n - 1) pairs; (i, i) leaves by index, a coincident point
+ *   contributes w = 1 and force 0.  fp32 terms (1 / x within an ulp of the rounded quotient), fp32 sums over one 256-point tile,
+ *   fp64 across tiles and splits, folded in a fixed order.  |y| < 1e18.
+ * tsne_gradient: the CSR (cap = entries col / p hold; rowptr is clamped to it and a column outside [0, n) is skipped), y, rep and Z
+ *   as tsne_repulsion wrote them -> grad [n][2] fp32 = 4 (exaggeration att_i - rep_i / Z), att_i = sum_j p_ij w_ij (y_i - y_j)
+ *   over row i, and kl[0] (device, fp64; NULL = not wanted, workspace may then be NULL) = sum_ij p_ij log(p_ij Z / w_ij) of the
+ *   UNexaggerated P, log and sum in fp64, folded in a fixed order.
+ * tsne_update: `_gradient_descent` of sklearn/manifold/_t_sne.py on every element, fp32, in place: inc = update grad < 0;
+ *   gains = max(inc ? gains + 0.2 : gains 0.8, 0.01); update = momentum update - learning_rate gains grad; y += update.
+ * y, rep and grad 8-byte aligned, workspaces 16-byte aligned (EALIGN).
+ * tsne_workspace (host): bytes that serve tsne_symmetrize (n, k), tsne_repulsion and tsne_gradient (n). */
+int audiossl_tsne_workspace(int n, int k, long* bytes);
+int audiossl_tsne_calibrate(const float* d2, int n, int k, double perplexity, float* p_cond, float* beta, void* stream);
+int audiossl_tsne_symmetrize(const int* idx, const float* p_cond, int n, int k, int* rowptr, int* col, float* p, int* nnz,
+                             void* workspace, long workspace_bytes, void* stream);
+int audiossl_tsne_repulsion(const float* y, int n, float* rep, double* Z, void* workspace, long workspace_bytes, void* stream);
+int audiossl_tsne_gradient(const int* rowptr, const int* col, const float* p, long cap, const float* y, const float* rep,
+                           const double* Z, int n, double exaggeration, float* grad, double* kl, void* workspace,
+                           long workspace_bytes, void* stream);
+int audiossl_tsne_update(const float* grad, int n, double momentum, double learning_rate, float* y, float* update, float* gains,
+                         void* stream);
+
 /* ---- K22 audio tagging (multi-label downstream, csrc/tagging.hip): nn.BCEWithLogitsLoss (the "bce_logit" of
  * `extras/mast_new/mast/mvit/models/losses.py:38`) on the multi-hot / mixed targets of `mast/dataloader.py:157-184` and the per-class metrics of
  * `extras/mast_new/mast/utilities/stats.py:11-57` (sklearn's average_precision_score / roc_auc_score, class by class on the host
