@@ -37,8 +37,9 @@ static inline hipError_t assl_zero_async(void* p, size_t bytes, hipStream_t s) {
     do { if (assl_zero_async((ptr), (bytes), (s)) != hipSuccess) return ASSL_ELAUNCH; } while (0)
 
 // Name of the kernel launched by the most recent entry point whose dispatch picks among several: the GEMM family (read back
-// through audiossl_last_kernel by bench.py so that its per-kernel table joins to rocprofv3's kernel names) and the two log-mel
-// entry points (block kernel or persistent kernel; the tests ask which one they ran).  Always a string that outlives the call.
+// through audiossl_last_kernel by bench.py so that its per-kernel table joins to rocprofv3's kernel names), the two log-mel
+// entry points (block kernel or persistent kernel; the tests ask which one they ran) and the 3x3 convolution (conv3x3_fwd,
+// conv3x3_pool_fwd, conv3x3_wgrad: "+reduce" follows the name when the fold runs).  Always a string that outlives the call.
 extern const char* g_assl_last_kernel;
 #define ASSL_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return ASSL_ELAUNCH; return ASSL_OK; } while (0)
 

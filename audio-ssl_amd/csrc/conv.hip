@@ -11,7 +11,8 @@
 //   pixels (8 rows x 32 or 16 rows x 16) whose (rows+2) x (F+2) halo is prefetched into registers during the MFMAs of
 //   the previous tile; a wave owns 64 pixels x 64 channels = 2x2 accumulators of v_mfma_f32_32x32x16_bf16, 36 k-steps
 //   (9 taps x 4 channel chunks), 1 ds_read_b128 per MFMA.  Optional epilogue: + bias, per-channel sum / sum of squares
-//   of the fp32 accumulators (BatchNorm batch statistics, fp64 atomics once per workgroup).
+//   of the values as stored, i.e. after the bf16 rounding of a bf16 output (BatchNorm batch statistics, fp64 atomics once per
+//   workgroup).
 // conv3x3_wgrad_kernel:  dW[co][tap*64+ci] += sum_pix dY[pix][co] * X[pix+tap][ci]
 //   k = pixels, so both operands are read from their row-major LDS tiles with ds_read_b64_tr_b16 (4 pixels x 16
 //   channels transposed per 16-lane group); the 64x576 fp32 result lives in registers (9 accumulators per wave) across
@@ -170,8 +171,9 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             v[e] = acc[i][j][4 * q + e] + bias4[j][q][e];
-                            ssum[j][4 * q + e] += v[e];
-                            ssq[j][4 * q + e] += v[e] * v[e];
+                            const float sv = a.out_f32 ? v[e] : (float)(bf16)v[e];       // the statistics are those of the value as stored
+                            ssum[j][4 * q + e] += sv;
+                            ssq[j][4 * q + e] += sv * sv;
                         }
                         const int co = j * 32 + 8 * q + 4 * h;
                         if (a.out_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.Y) + o + co) = v;
@@ -770,6 +772,7 @@ extern "C" int audiossl_conv3x3_fwd(const void* X, const void* W, const float* b
         const size_t lds = 2 * WsGeom<FI_>::BYTES + sizeof(float) * (64 + 4 * 64 * 2) + 4 * 64 * (F32_ ? 256 : 128) + 512; \
         if (!wattr[SLOT]) { if (set_lds(conv3x3_ws_kernel<FI_, ST_, F32_>, lds)) return ASSL_ELAUNCH; wattr[SLOT] = true; } \
         hipLaunchKernelGGL((conv3x3_ws_kernel<FI_, ST_, F32_>), dim3(grid), dim3(256), lds, s, a);       \
+        g_assl_last_kernel = "conv3x3_ws_kernel<" #FI_ ", " #ST_ ", " #F32_ ">";                         \
     } while (0)
         if (Fi == 32) {
             if (sum && !(conv_dbg & 16)) { if (out_f32) WS_LAUNCH(32, true, true, 0); else WS_LAUNCH(32, true, false, 1); }
@@ -788,6 +791,7 @@ extern "C" int audiossl_conv3x3_fwd(const void* X, const void* W, const float* b
         const size_t lds = sizeof(bf16) * (CH * WPITCH + Halo<FI_, PIXP>::ELEMS);                         \
         if (!attr[SLOT]) { if (set_lds(conv3x3_kernel<FI_, NW_>, lds)) return ASSL_ELAUNCH; attr[SLOT] = true; } \
         hipLaunchKernelGGL((conv3x3_kernel<FI_, NW_>), dim3(grid), dim3(64 * NW_), lds, s, a);           \
+        g_assl_last_kernel = "conv3x3_kernel<" #FI_ ", " #NW_ ">";                                       \
     } while (0)
     if (Fi == 32) { if (nw == 8) CONV_LAUNCH(32, 8, 0); else CONV_LAUNCH(32, 4, 1); }
     else          { if (nw == 8) CONV_LAUNCH(16, 8, 2); else CONV_LAUNCH(16, 4, 3); }
@@ -821,6 +825,7 @@ extern "C" int audiossl_conv3x3_pool_fwd(const void* X, const void* W, const flo
         const size_t lds = 2 * WsGeom<FI_>::BYTES + sizeof(float) * (64 + 4 * 64 * 2) + 4 * 64 * 128 + 512 + 256; \
         if (!pattr[SLOT]) { if (set_lds(conv3x3_ws_kernel<FI_, true, false, 2, true, KEEP_>, lds)) return ASSL_ELAUNCH; pattr[SLOT] = true; } \
         hipLaunchKernelGGL((conv3x3_ws_kernel<FI_, true, false, 2, true, KEEP_>), dim3(grid), dim3(256), lds, s, a); \
+        g_assl_last_kernel = "conv3x3_ws_kernel<" #FI_ ", true, false, 2, true, " #KEEP_ ">";            \
     } while (0)
     if (Fi == 32) { if (Y) POOL_LAUNCH(32, true, 0); else POOL_LAUNCH(32, false, 1); }
     else          { if (Y) POOL_LAUNCH(16, true, 2); else POOL_LAUNCH(16, false, 3); }
@@ -854,6 +859,7 @@ extern "C" int audiossl_conv3x3_wgrad(const void* dY, const void* X, float* dWp,
         const size_t lds = max(sizeof(bf16) * (256 * PIXW + Halo<FI_, PIXW>::ELEMS), (size_t)(KG_ == 2 ? 4 * 9 * 16 * 64 * 4 : 0)); \
         if (!attr[SLOT]) { if (set_lds(conv3x3_wgrad_kernel<FI_, KG_>, lds)) return ASSL_ELAUNCH; attr[SLOT] = true; } \
         hipLaunchKernelGGL((conv3x3_wgrad_kernel<FI_, KG_>), dim3(grid), dim3(256 * KG_), lds, s, a);    \
+        g_assl_last_kernel = two_stage ? "conv3x3_wgrad_kernel<" #FI_ ", " #KG_ ">+reduce" : "conv3x3_wgrad_kernel<" #FI_ ", " #KG_ ">"; \
     } while (0)
     if (Fi == 32) { if (kg == 2) WGRAD_LAUNCH(32, 2, 0); else WGRAD_LAUNCH(32, 1, 1); }
     else          { if (kg == 2) WGRAD_LAUNCH(16, 2, 2); else WGRAD_LAUNCH(16, 1, 3); }

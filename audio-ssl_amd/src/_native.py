@@ -137,7 +137,7 @@ _GEMM_FAMILY = {"audiossl_gemm", "audiossl_gemm_dropout", "audiossl_gemm_multi",
 
 
 def last_kernel():
-    """Name (rocprofv3 spelling) of the kernel the most recent GEMM-family or log-mel call launched."""
+    """Name (rocprofv3 spelling) of the kernel the most recent GEMM-family, log-mel or 3x3 convolution call launched."""
     buf = ctypes.create_string_buffer(128)
     rc = lib().audiossl_last_kernel(ctypes.addressof(buf), 128)
     if rc != 0:

@@ -411,7 +411,9 @@ int audiossl_set_prezeroed(int on);
 /* Host-side query (diagnostics): the kernel the most recent audiossl_gemm / gemm_multi / gemm_multi_barlow / moco_logits call
  * launched, as a substring of the name rocprofv3 prints for it ("gemm_sp_multi_kernel<false, false, 6>"; instantiations on the bf16
  * type appear mangled there: "gemm_multi_kernelIDF16bLb0ELb0ELi64ELi2ELi4E").  The dispatch picks among several instantiations
- * by shape; bench.py's per-kernel roofline table uses this to join its rows to profiles/ kernel_stats.csv. */
+ * by shape; bench.py's per-kernel roofline table uses this to join its rows to profiles/ kernel_stats.csv.
+ * The log-mel entry points and conv3x3_fwd / conv3x3_pool_fwd / conv3x3_wgrad record theirs too ("conv3x3_ws_kernel<32, true, false>",
+ * "conv3x3_kernel<16, 4>", "conv3x3_wgrad_kernel<32, 2>+reduce" when the fold of the per-workgroup results follows). */
 int audiossl_last_kernel(char* name, int capacity);
 
 /* ---- K17 optimiser + plumbing: delores_s/upstream_expert.py:236-243 (torch.optim.SGD) ---------------------- */

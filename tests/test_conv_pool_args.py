@@ -1,4 +1,4 @@
-"""CPU: conv3x3_pool_fwd and the pooled BatchNorm entries reject bad arguments before any launch (no GPU is touched: the
+"""CPU: conv3x3_fwd, conv3x3_wgrad, conv3x3_pool_fwd and the pooled BatchNorm entries reject bad arguments before any launch (no GPU is touched: the
 pointers are made-up, 16-byte aligned addresses that a launch would fault on)."""
 from src import _native as N
 
@@ -18,6 +18,35 @@ def test_conv_pool_fwd_rejects_what_it_cannot_pool():
     assert pool_fwd(q=A + 1024) == -1 and pool_fwd(rep=0) == -1 and pool_fwd(rep=65) == -1      # replicas: sumsq == sum + 64 doubles
     assert pool_fwd(n=1 << 20, Ti=64) == -1                         # past the 2 GB a 32-bit buffer offset reaches
     assert pool_fwd(Praw=A + 8) == -3 and pool_fwd(Y=A + 2) == -3
+
+
+def conv_fwd(X=A, W=A, bias=A, Y=A, f32=0, s=A, q=A + 512, rep=1, n=3, Ti=6, Fi=32):
+    return N.lib().audiossl_conv3x3_fwd(X, W, bias, Y, f32, s, q, rep, n, Ti, Fi, None)
+
+
+def test_conv_fwd_rejects_bad_arguments():
+    assert conv_fwd(X=None) == -1 and conv_fwd(W=None) == -1 and conv_fwd(Y=None) == -1
+    assert conv_fwd(n=0) == -1 and conv_fwd(n=-1) == -1 and conv_fwd(Ti=0) == -1 and conv_fwd(Ti=-3) == -1
+    assert conv_fwd(Fi=8) == -1 and conv_fwd(Fi=64) == -1 and conv_fwd(Fi=0) == -1 and conv_fwd(Fi=24) == -1
+    assert conv_fwd(q=None) == -1 and conv_fwd(s=None) == -1                # the statistics come as a pair or not at all
+    assert conv_fwd(rep=0) == -1 and conv_fwd(rep=65) == -1 and conv_fwd(rep=-1) == -1
+    assert conv_fwd(rep=8, q=A + 1024) == -1 and conv_fwd(rep=2, q=A + 256) == -1      # replicas: sumsq == sum + 64 doubles
+    for f32 in (0, 1):
+        assert conv_fwd(X=A + 8, f32=f32) == -3 and conv_fwd(W=A + 2, f32=f32) == -3 and conv_fwd(Y=A + 4, f32=f32) == -3
+    assert conv_fwd(X=A + 8, s=None, q=None) == -3
+    assert conv_fwd(X=None, Y=A + 4) == -1                                  # a null pointer is reported before a misaligned one
+
+
+def conv_wgrad(dY=A, X=A, dWp=A, ws=None, ws_floats=0, n=3, Ti=6, Fi=32):
+    return N.lib().audiossl_conv3x3_wgrad(dY, X, dWp, ws, ws_floats, n, Ti, Fi, None)
+
+
+def test_conv_wgrad_rejects_bad_arguments():
+    assert conv_wgrad(dY=None) == -1 and conv_wgrad(X=None) == -1 and conv_wgrad(dWp=None) == -1
+    assert conv_wgrad(Fi=8) == -1 and conv_wgrad(Fi=64) == -1 and conv_wgrad(Fi=0) == -1
+    assert conv_wgrad(n=0) == -1 and conv_wgrad(Ti=0) == -1
+    assert conv_wgrad(X=A + 8) == -3 and conv_wgrad(dY=A + 2) == -3
+    assert conv_wgrad(X=A + 8, ws=A, ws_floats=1 << 30) == -3
 
 
 def test_pooled_bn_entries_reject_null_and_empty():

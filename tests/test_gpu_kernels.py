@@ -483,7 +483,7 @@ def test_conv3x3_implicit_gemm_fwd_dgrad_wgrad(N, shape):
     N.call("pack_conv_w", 1, w2, Wf2, Wd2)
     torch.cuda.synchronize()
     assert torch.equal(pk[0], Wf) and torch.equal(pk[1], Wd) and torch.equal(pk[2], Wf2) and torch.equal(pk[3], Wd2)
-    wq = Wf.float().view(64, 9, 64).permute(0, 2, 1).reshape(64, 64, 3, 3)                        # bf16-rounded [co][ci][kh][kw]
+    wq = w.bfloat16().float()                    # bf16-rounded [co][ci][kh][kw], from w itself: the packing is under test too
     x_nchw = x.float().permute(0, 3, 2, 1).contiguous()                                           # [N][C][F][T]
     ref = Fnn.conv2d(x_nchw.double(), wq.double(), b.double(), padding=1)                         # [N][co][F][T]
     Y = torch.full((Nimg, Ti, Fi, 64), float("nan"), device="cuda", dtype=torch.bfloat16)
