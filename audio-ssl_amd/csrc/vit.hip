@@ -8,6 +8,7 @@
 //                          the flat parameter buffer, step count read from device memory (graph replay advances it)
 // The residual stream is fp32; LayerNorm writes the bf16 MFMA operand; every gradient entering a LayerNorm backward is fp32.
 #include "common.h"
+#include "adamw.h"
 
 namespace {
 
@@ -298,32 +299,23 @@ __global__ __launch_bounds__(256) void tile_rows_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
                                                     float gscale, const long long* __restrict__ step) {
-    const float t = (float)step[0];
-    const float bc1 = 1.f - powf(b1, t), bc2s = sqrtf(1.f - powf(b2, t));
-    const float step_size = lr / bc1;
+    float step_size, bc2s;
+    adamw_bias(step, lr, b1, b2, step_size, bc2s);
     for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
         if (i + 4 <= n) {
             f32x4 pv = *reinterpret_cast<f32x4*>(p + i), mv = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
             const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float gg = gv[k] * gscale;
-                pv[k] *= 1.f - lr * wd;
-                mv[k] = b1 * mv[k] + (1.f - b1) * gg;
-                vv[k] = b2 * vv[k] + (1.f - b2) * gg * gg;
-                pv[k] -= step_size * mv[k] / (sqrtf(vv[k]) / bc2s + eps);
+                float pk = pv[k], mk = mv[k], vk = vv[k];
+                adamw_elem(pk, gv[k], mk, vk, lr, wd, b1, 1.f - b1, b2, 1.f - b2, eps, gscale, step_size, bc2s);
+                pv[k] = pk; mv[k] = mk; vv[k] = vk;
             }
             *reinterpret_cast<f32x4*>(p + i) = pv;
             *reinterpret_cast<f32x4*>(m + i) = mv;
             *reinterpret_cast<f32x4*>(v + i) = vv;
         } else {
-            for (long j = i; j < n; ++j) {
-                const float gg = g[j] * gscale;
-                float pj = p[j] * (1.f - lr * wd);
-                m[j] = b1 * m[j] + (1.f - b1) * gg;
-                v[j] = b2 * v[j] + (1.f - b2) * gg * gg;
-                p[j] = pj - step_size * m[j] / (sqrtf(v[j]) / bc2s + eps);
-            }
+            for (long j = i; j < n; ++j) adamw_elem(p[j], g[j], m[j], v[j], lr, wd, b1, 1.f - b1, b2, 1.f - b2, eps, gscale, step_size, bc2s);
         }
     }
 }

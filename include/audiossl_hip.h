@@ -733,6 +733,34 @@ int audiossl_larc_step(float* p, const float* g, float* mu, const void* seg, int
                        float momentum, float trust_coefficient, float eps, int clip, float grad_scale, double* norms,
                        void* stream);
 
+/* ---- Linear evaluation on cached embeddings: a grid of H heads trained together (csrc/probe.hip, src/evaluation/probe.py).
+ * The heads are one fp32 matrix W [H * Cp][Dp], Cp = C rounded up to a multiple of 8: head h owns rows [h Cp, h Cp + C), its
+ * pad rows are zero and never move (their gradient is exactly zero).  Dp = D + 8: the batch carries 1.0 in column D, so the
+ * bias is column D of W and is decayed like the weights, as torch.optim.AdamW(linear.parameters(), weight_decay) does.  The two
+ * GEMMs of a step are audiossl_gemm with dtype 0: logits [B][H Cp] = Xb W^T and dW = G^T Xb (both transposes set: any B).
+ * probe_batch: out[r][0:D] = (X[idx[r]][:] - mean[:]) * rstd[:] in fp32, subtract then multiply, each rounded once (equal to
+ *   numpy fp32 bit for bit); mean and rstd NULL together = a plain gather.  out[r][D] = 1, out[r][D+1 : ldo] = 0.  X [N][D]
+ *   row-major, idx int32 [B] on the device, rows may repeat.  An index outside [0, N) is never dereferenced: all ldo columns of
+ *   its row are NaN.  D % 8 == 0, 8 <= D <= 4096, ldo >= D + 8, ldo % 4 == 0.
+ * probe_ce: for every row r and head h, over columns [h Cp, h Cp + C) of logits [B][ld]: stable soft-max cross-entropy against
+ *   label[r] (int64).  loss_sum[h] (fp64) += the sum of the row losses, correct[h] (int64) += the rows whose first arg-max (ties
+ *   to the lowest class, as torch.argmax) equals the label; both have one writer that sums in a fixed order, no atomics: two
+ *   launches on the same input agree bit for bit.  dlogits[r][h Cp + c] = gscale (p - 1[c == label]) for c < C and exactly 0
+ *   for the pad columns; columns at and beyond H Cp are not touched.  dlogits NULL = evaluation, the same loss_sum and correct
+ *   bit for bit.  A label outside [0, C) is never used as an index: it adds NaN to every loss_sum[h], and that row's class
+ *   columns of dlogits are NaN (pad columns still 0).  2 <= C <= 4096, Cp >= C, Cp % 4 == 0, H >= 1, ld >= H Cp, ld % 4 == 0.
+ * probe_adamw: torch.optim.AdamW with one parameter group per head: segment h = [h seg, (h + 1) seg) of the flat W / dW / m / v
+ *   uses lr[h] * lr_scale and wd[h] (device fp32 [H]); `step` = device int64 holding the 1-based count, as in audiossl_adamw,
+ *   whose per-element arithmetic this is (csrc/adamw.h); the betas are fp64, and 1 - beta and the two bias corrections are
+ *   formed in fp64 before they are rounded, as torch forms them on the host.  A head with lr = 0 and wd = 0 keeps W bit-unchanged.  seg % 4 == 0.
+ * None of the three synchronises with the host; all validate before any launch. */
+int audiossl_probe_batch(const float* X, long N, int D, const int* idx, int B, const float* mean, const float* rstd, float* out,
+                         long ldo, void* stream);
+int audiossl_probe_ce(const float* logits, long ld, const long long* label, int B, int H, int C, int Cp, float gscale,
+                      double* loss_sum, long long* correct, float* dlogits, void* stream);
+int audiossl_probe_adamw(float* W, const float* dW, float* m, float* v, int H, long seg, const float* lr, const float* wd,
+                         float lr_scale, double beta1, double beta2, float eps, const long long* step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
