@@ -10,10 +10,19 @@ PCA-whiten, cluster, and write the `files,label` CSV `train_upstream.py --upstre
         --k_sweep 64,128,256 --out labelled.csv
     python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv --k 585 \
         --out labelled.csv --map map.csv
+    python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv \
+        --clustering spread --seed_labels few.csv --drop_unreached --out labelled.csv
 
 `--clustering kmeans` (the default) needs `--k`.  `--clustering pic` is the reference's other algorithm (`PIC`, imported next to
 `Kmeans` at `store_clusters.py:18`): power-iteration clustering on an exact nearest-neighbour graph, which finds the number of
 clusters itself; the summary line prints that number, which is what `pretrain.task_label` has to be set to.
+`--clustering spread --seed_labels few.csv` is for the user who HAS labels for a few files: `few.csv` is a `files,label` CSV whose
+files are a subset of `--input`; its label values, sorted as strings, become the ids 0 .. C - 1 (the mapping is printed) and label
+spreading (`src.evaluation.spread.label_spread`, Zhou et al. 2004) carries them over the exact nearest-neighbour graph of the
+whitened features (`--nnn`, `--sigma`; `--spread_alpha`, `--spread_iters`) to every other file, so the ids written ARE the
+user's classes.  Seed files keep the label they came with.  A file no seed reaches is written with label -1 and counted in the
+summary line; `--drop_unreached` leaves those files out of `--out` (UnFuSeD needs 0 .. C - 1); `--confidence` adds a third column,
+1 - H(p) / log C of the file's class distribution.  The reference has no counterpart.
 `--compare other.csv` prints the normalised mutual information between the labels just written and those of another
 `files,label` file over the same files (a k-means labeling against a PIC one, or pseudo-labels against real ones).
 `--score` prints the silhouette coefficient (sklearn's `silhouette_score`, Euclidean) of the labels just written on the whitened
@@ -76,6 +85,46 @@ def sweep_kmeans(feats, ks, pca, verbose=False):
     return model, loss, score
 
 
+def read_seed_labels(path, files):
+    """`files,label` CSV whose files are a subset of `files` -> (row of every seed in `files`, its class id, class names): label
+    values sorted as strings become 0 .. C - 1.  Anything else is a ValueError naming the first offender."""
+    few = pd.read_csv(path)
+    for column in ("files", "label"):
+        if column not in few.columns:
+            raise ValueError(f"{path} has no `{column}` column")
+    if len(few) == 0:
+        raise ValueError(f"{path} lists no file")
+    where = {}
+    for i, f in enumerate(files):
+        where.setdefault(f, i)
+    names = sorted(set(few["label"]), key=str)
+    label2id = {k: i for i, k in enumerate(names)}
+    rows, ids, seen = [], [], set()
+    for f, v in zip(few["files"], few["label"]):
+        if f not in where:
+            raise ValueError(f"{path}: {f} is not a file of --input")
+        if f in seen:
+            raise ValueError(f"{path}: {f} is listed more than once")
+        seen.add(f)
+        rows.append(where[f])
+        ids.append(label2id[v])
+    return np.asarray(rows, dtype=np.int64), np.asarray(ids, dtype=np.int64), [str(k) for k in names]
+
+
+def spread_labels(feats, rows, ids, classes, pca, nnn, sigma, alpha, iters=None):
+    """-> (whitened features, label per file as int64 numpy with -1 = unreached, confidence per file): one trial of label spreading
+    from the seeds (rows, ids) on the graph PIC would build; seeds keep their label."""
+    from src.evaluation.graph import knn_graph, pic_build
+    from src.evaluation.spread import label_spread
+    xb = preprocess_features(feats, pca=pca)
+    idx, d2 = knn_graph(xb, min(nnn, xb.shape[0] - 1))
+    W = pic_build(idx, d2, sigma)
+    res = label_spread(W, torch.from_numpy(rows), torch.from_numpy(ids), classes, classes, alpha=alpha, iters=iters)
+    labels = res.labels[:, 0].cpu().numpy().astype(np.int64)
+    labels[rows] = ids
+    return xb, labels, res.confidence[:, 0].cpu().numpy()
+
+
 def main(args):
     from src.evaluation.embed import extract_embeddings, load_embedder
     if not torch.cuda.is_available():
@@ -85,6 +134,8 @@ def main(args):
         with open(args.config, "r") as f:
             config = yaml.load(f, Loader=yaml.SafeLoader)
     files = list(pd.read_csv(args.input)["files"])
+    if args.clustering == "spread":
+        seed_rows, seed_ids, names = read_seed_labels(args.seed_labels, files)       # a bad seed file: refused before the embedding
     if args.map:
         from src.evaluation.tsne import neighbour_count
         neighbour_count(len(files), args.perplexity)                     # a perplexity the map cannot have: refused before the embedding
@@ -101,6 +152,19 @@ def main(args):
         model.cluster(feats, verbose=args.verbose, pca=pca)
         labels = write_pseudolabel_csv(files, model, args.out, header="files,label")
         print(f"{len(files)} files, {len(model.images_lists)} clusters, pic sigma {args.sigma:g} nnn {args.nnn} -> {args.out}")
+        features = model.features
+    elif args.clustering == "spread":
+        print("classes: " + ", ".join(f"{i}={name}" for i, name in enumerate(names)))
+        features, labels, conf = spread_labels(feats, seed_rows, seed_ids, len(names), pca, args.nnn, args.sigma, args.spread_alpha,
+                                               args.spread_iters)
+        unreached = int((labels < 0).sum())
+        with open(args.out, "w") as f:
+            f.write("files,label,confidence\n" if args.confidence else "files,label\n")
+            for p, l, c in zip(files, labels, conf):
+                if l >= 0 or not args.drop_unreached:
+                    f.write(f"{p},{int(l)},{float(c):.6f}\n" if args.confidence else f"{p},{int(l)}\n")
+        print(f"{len(files)} files, {len(names)} classes from {len(seed_rows)} seeds, {unreached} unreached"
+              f"{' (dropped)' if args.drop_unreached else ''}, spread sigma {args.sigma:g} nnn {args.nnn} alpha {args.spread_alpha:g} -> {args.out}")
     else:
         if args.k_sweep:
             model, loss, chosen = sweep_kmeans(feats, args.k_sweep, pca, verbose=args.verbose)
@@ -109,12 +173,13 @@ def main(args):
             loss = model.cluster(feats, verbose=args.verbose, pca=pca)
         labels = write_pseudolabel_csv(files, model, args.out, header="files,label")
         print(f"{len(files)} files, {model.k} clusters, k-means loss {loss:.6g} -> {args.out}")
+        features = model.features
     if args.score:
-        score, count, singles = _silhouette(model.features, labels)
+        score, count, singles = _silhouette(features, labels)
         print(f"silhouette {_fmt(score)} ({count} clusters, {singles} singletons)")
     if args.map:
         from src.evaluation.tsne import tsne
-        y, kl = tsne(model.features, perplexity=args.perplexity, n_iter=args.map_iters, return_kl=True)
+        y, kl = tsne(features, perplexity=args.perplexity, n_iter=args.map_iters, return_kl=True)
         y = y.cpu().numpy()
         pd.DataFrame({"files": files, "label": [int(c) for c in labels], "x": y[:, 0], "y": y[:, 1]}).to_csv(args.map, index=False)
         print(f"map of {len(files)} files, perplexity {args.perplexity:g}, {args.map_iters} iterations, KL {kl:.6f} -> {args.map}")
@@ -141,20 +206,25 @@ def _k_list(text):
 
 
 def get_args(argv=None):
-    parser = argparse.ArgumentParser(allow_abbrev=False, description="checkpoint -> embeddings -> k-means or PIC pseudo-labels")
+    parser = argparse.ArgumentParser(allow_abbrev=False, description="checkpoint -> embeddings -> k-means, PIC or seeded (label spreading) pseudo-labels")
     parser.add_argument("--checkpoint", type=str, required=True)
     parser.add_argument("--upstream", type=str, default="delores_m")
     parser.add_argument("--input", type=str, required=True, help="csv with a `files` column")
-    parser.add_argument("--clustering", choices=("kmeans", "pic"), default="kmeans")
+    parser.add_argument("--clustering", choices=("kmeans", "pic", "spread"), default="kmeans")
     parser.add_argument("--k", type=int, default=None, help="number of clusters for k-means (the reference uses 585); ignored by pic")
     parser.add_argument("--k_sweep", type=_k_list, default=None,
                         help="k-means: comma-separated k values in place of --k; the k with the highest silhouette is written")
     parser.add_argument("--out", type=str, required=True, help="`files,label` csv to write")
     parser.add_argument("--pca", type=int, default=128)
-    parser.add_argument("--sigma", type=float, default=0.2, help="pic: bandwidth of the Gaussian kernel")
-    parser.add_argument("--nnn", type=int, default=5, help="pic: nearest neighbours per node")
+    parser.add_argument("--sigma", type=float, default=0.2, help="pic, spread: bandwidth of the Gaussian kernel")
+    parser.add_argument("--nnn", type=int, default=5, help="pic, spread: nearest neighbours per node")
     parser.add_argument("--alpha", type=float, default=0.001, help="pic: damping of the power iteration")
     parser.add_argument("--no_distribute_singletons", action="store_true", help="pic: keep one-member clusters")
+    parser.add_argument("--seed_labels", type=str, default=None, help="spread: `files,label` csv of the labelled files (a subset of --input)")
+    parser.add_argument("--spread_alpha", type=float, default=0.99, help="spread: share of a node's value that comes from its neighbours")
+    parser.add_argument("--spread_iters", type=int, default=None, help="spread: rounds (default: until spread_alpha^iters <= 1e-3)")
+    parser.add_argument("--drop_unreached", action="store_true", help="spread: leave files no seed reaches out of --out")
+    parser.add_argument("--confidence", action="store_true", help="spread: a third column, 1 - H(p) / log C")
     parser.add_argument("--compare", type=str, default=None, help="another `files,label` csv: print the NMI against it")
     parser.add_argument("--score", action="store_true", help="print the silhouette coefficient of the labels just written")
     parser.add_argument("--map", type=str, default=None, help="`files,label,x,y` csv to write: a 2-D t-SNE map of the whitened features")
@@ -172,6 +242,17 @@ def get_args(argv=None):
         parser.error("--k_sweep takes the place of --k: give one of them")
     if args.k_sweep is not None and args.clustering == "pic":
         parser.error("--k_sweep is for k-means: pic finds the number of clusters itself")
+    if args.clustering == "spread":
+        if args.k is not None or args.k_sweep is not None:
+            parser.error("--k and --k_sweep are for k-means: spread takes its classes from --seed_labels")
+        if args.seed_labels is None:
+            parser.error("--clustering spread needs --seed_labels")
+        if not 0.0 < args.spread_alpha < 1.0:
+            parser.error("--spread_alpha must be in (0, 1)")
+        if args.spread_iters is not None and args.spread_iters < 1:
+            parser.error("--spread_iters must be positive")
+    elif args.seed_labels is not None or args.drop_unreached or args.confidence:
+        parser.error("--seed_labels, --drop_unreached and --confidence go with --clustering spread")
     if args.clustering == "kmeans" and args.k is None and args.k_sweep is None:
         parser.error("the following arguments are required: --k")       # argparse's own wording for a required option
     return args

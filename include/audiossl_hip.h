@@ -568,6 +568,33 @@ int audiossl_pic_power(const int* rowptr, const int* col, const double* w, int n
 int audiossl_pic_assign(const int* rowptr, const int* col, const double* w, const double* v, int n, long cap, int* label,
                         int* count, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- label spreading on the same graph (csrc/spread.hip): Zhou et al. 2004, sklearn's `LabelSpreading`; the reference has no
+ * counterpart.  S = D^-1/2 W D^-1/2, F_0 = Y, F <- alpha S F + (1 - alpha) Y on an [n][m] block whose m columns are independent
+ * problems (classes x trials of a low-shot evaluation).  No float atomics: two calls agree bit for bit, and a column's result
+ * does not depend on which other columns share the call; the workspace needs no clearing; nothing synchronises with the host.
+ * Every entry returns EINVAL for a null pointer before any launch.
+ * spread_workspace (host): bytes for spread_run (the second F buffer), non-decreasing in n and in m; refuses what spread_run does.
+ * spread_normalize: the CSR of pic_build (`cap` = entries col / w / s hold; rowptr is clamped to it, a column outside [0, n) gives
+ *   s = 0 and adds nothing to deg) -> deg [n] fp64 = row sums in column order; s [cap] fp32, s_l = (float)(w_l / sqrt(deg_i deg_j))
+ *   for entry l = (i, j), product, root and quotient in fp64: s_ij == s_ji bit for bit.  A zero product gives s_l = 0 (a node whose
+ *   weights all underflowed): no inf, no NaN.  Entries no row points at are not written.  n >= 2, cap >= 0.
+ * spread_run: Y is never stored: Y[i][seed_col[q]] = 1 for q in seed_ptr[i] .. seed_ptr[i + 1] - 1 (seed_ptr [n + 1], clamped to
+ *   `seeds`; a seed_col outside [0, m) is skipped).  f [n][m] fp32 = F after `iters` rounds; fp32 storage, every value one fmaf
+ *   chain over its row's entries in column order, then fmaf(alpha, sum, (1 - alpha) Y).  A column outside [0, n) is skipped.
+ *   n >= 2, 4 <= m <= 16384, m % 4 == 0 (pad with empty columns), n m < 2^31, 0 < alpha < 1, 1 <= iters <= 10^6, seeds >= 0,
+ *   cap >= 0, workspace_bytes >= spread_workspace (EINVAL); f and workspace 16-byte aligned (EALIGN).
+ * spread_assign: f [n][ldf]; trial t owns columns t classes .. (t + 1) classes - 1.  label [n][trials] = arg-max over them, ties to
+ *   the lowest class, -1 when the largest value is <= 0 (unreached).  confidence [n][trials] fp32 = 1 - H(p) / log(classes),
+ *   p = row / sum(row) over the positive entries (Iscen et al. 2019, eq. 11), in fp64 from the fp32 row; 0 for an unreached row,
+ *   else 1 when classes == 1.  n, classes, trials >= 1, classes trials <= ldf, n ldf < 2^31. */
+int audiossl_spread_workspace(int n, int m, long* bytes);
+int audiossl_spread_normalize(const int* rowptr, const int* col, const double* w, int n, long cap, double* deg, float* s,
+                              void* stream);
+int audiossl_spread_run(const int* rowptr, const int* col, const float* s, int n, long cap, const int* seed_ptr,
+                        const int* seed_col, int seeds, int m, double alpha, int iters, float* f, void* workspace,
+                        long workspace_bytes, void* stream);
+int audiossl_spread_assign(const float* f, int n, int ldf, int classes, int trials, int* label, float* confidence, void* stream);
+
 /* ---- silhouette coefficient of a labeling on its features (csrc/silhouette.hip): sklearn's `silhouette_samples`, Euclidean -------
  * The label-free score of a pseudo-labeling (`store_clusters --score`, `--k_sweep`); the reference has no counterpart.
  * silhouette: xs [n][d] row-major fp32, rows SORTED BY CLUSTER; seg [K + 1] int32 offsets (device): cluster c is rows seg[c] ..
