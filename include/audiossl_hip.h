@@ -568,6 +568,41 @@ int audiossl_pic_power(const int* rowptr, const int* col, const double* w, int n
 int audiossl_pic_assign(const int* rowptr, const int* col, const double* w, const double* v, int n, long cap, int* label,
                         int* count, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- exact range search and connected components (csrc/range.hip): every pair of rows closer than a radius - near-duplicates
+ * inside one file list, leakage between two; faiss `range_search` in the reference's stack.  The output length is not known before
+ * the launch: range_count, one host read of `total`, range_fill.  Every workspace is device memory that needs no clearing; two
+ * calls on the same inputs agree bit for bit (no float atomics); nothing synchronises with the host.  Every entry returns EINVAL for
+ * a null pointer or a refused shape before any launch, EALIGN for x or a workspace that is not 16-byte aligned.
+ * range_workspace (host): bytes for range_count / range_fill (the norms of all n rows + the per-(row, split) counts), non-decreasing
+ *   in each argument: a workspace sized for a forced `splits` also serves splits = 0.  1 <= rows <= n, 0 <= splits <= 64.
+ * range_count: x [n][d] row-major fp32, d % 4 == 0 (pad with zero columns), 4 <= d <= 4096; owned rows [own_lo, own_hi), walked
+ *   rows [walk_lo, walk_hi), both non-empty and inside [0, n); r2 >= 0 and finite.  For every owned row i it counts the walked
+ *   rows j != i with d2_ij <= r2, d2_ij = max(0, (n_i + n_j) - 2 g_ij): knn_graph_l2's arithmetic (fp32-input MFMA, an fmaf chain
+ *   over d in index order, n_i = g_ii by the same chain), so a repeated row is at distance exactly 0 and d2_ij == d2_ji bit for
+ *   bit.  i == j leaves by index: a duplicate row IS a match.  rowptr [rows + 1] int32, rows = own_hi - own_lo: the exclusive scan
+ *   of the counts, formed on the device.  total [1] (64-bit, 8-byte aligned): the true number of matches, also when it does not
+ *   fit int32 - rowptr is then unspecified and the caller must refuse.  splits: 0 = the library chooses how many workgroups share
+ *   one 64-row block's walk (few rows must not leave the chip idle), 1..64 forces it (capped at the number of 128-row tiles).
+ * range_fill: the same geometry, r2 and splits, and the workspace range_count left; `total` as read from range_count.  col [cap]
+ *   int32 = the ABSOLUTE row index j, d2 [cap] fp32; row i's entries at rowptr[i] .., in ascending j - a strict order, so the
+ *   result does not depend on splits or on how tiles are walked.  cap < total, total < 0 or total >= 2^31: EINVAL, nothing is
+ *   written.  Entries at or past `total` are not written (every store is bounded by it on the device as well).
+ * graph_components: weakly connected components of a CSR graph on n >= 1 nodes: an entry (i, j) links i and j whether or not
+ *   (j, i) is stored.  `cap` = entries col holds (rowptr [n + 1] is clamped to it, a column outside [0, n) is skipped, as in
+ *   pic_power).  label [n] int32 = the number of i's component when components are ordered by their smallest member (pic_assign's
+ *   convention), count [0] = the number of components.  One hook kernel (integer compare-and-swap, larger root under smaller: the
+ *   fixed point is unique, so the result is deterministic) and ceil(log2 n) rounds of pointer doubling.
+ * graph_components_workspace (host): bytes for graph_components, non-decreasing in n. */
+int audiossl_range_workspace(int n, int rows, int splits, long* bytes);
+int audiossl_range_count(const float* x, int n, int d, int own_lo, int own_hi, int walk_lo, int walk_hi, float r2, int splits,
+                         int* rowptr, long long* total, void* workspace, long workspace_bytes, void* stream);
+int audiossl_range_fill(const float* x, int n, int d, int own_lo, int own_hi, int walk_lo, int walk_hi, float r2, int splits,
+                        const int* rowptr, long long total, int* col, float* d2, long cap, void* workspace, long workspace_bytes,
+                        void* stream);
+int audiossl_graph_components_workspace(int n, long* bytes);
+int audiossl_graph_components(const int* rowptr, const int* col, int n, long cap, int* label, int* count, void* workspace,
+                              long workspace_bytes, void* stream);
+
 /* ---- label spreading on the same graph (csrc/spread.hip): Zhou et al. 2004, sklearn's `LabelSpreading`; the reference has no
  * counterpart.  S = D^-1/2 W D^-1/2, F_0 = Y, F <- alpha S F + (1 - alpha) Y on an [n][m] block whose m columns are independent
  * problems (classes x trials of a low-shot evaluation).  No float atomics: two calls agree bit for bit, and a column's result
