@@ -12,6 +12,8 @@ PCA-whiten, cluster, and write the `files,label` CSV `train_upstream.py --upstre
         --out labelled.csv --map map.csv
     python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv \
         --clustering spread --seed_labels few.csv --drop_unreached --out labelled.csv
+    python -m src.upstream.decar_v2.store_clusters --checkpoint final.ckpt --upstream delores_m --input files.csv \
+        --clustering hdbscan --min_cluster_size 25 --min_samples 5 --drop_unreached --out labelled.csv
 
 `--clustering kmeans` (the default) needs `--k`.  `--clustering pic` is the reference's other algorithm (`PIC`, imported next to
 `Kmeans` at `store_clusters.py:18`): power-iteration clustering on an exact nearest-neighbour graph, which finds the number of
@@ -23,6 +25,12 @@ whitened features (`--nnn`, `--sigma`; `--spread_alpha`, `--spread_iters`) to ev
 user's classes.  Seed files keep the label they came with.  A file no seed reaches is written with label -1 and counted in the
 summary line; `--drop_unreached` leaves those files out of `--out` (UnFuSeD needs 0 .. C - 1); `--confidence` adds a third column,
 1 - H(p) / log C of the file's class distribution.  The reference has no counterpart.
+`--clustering hdbscan` is for file lists full of clips that belong NOWHERE (MUSAN, web crawls): every other algorithm here forces
+each of them into a cluster, and each becomes a wrong pseudo-label.  HDBSCAN (`src.evaluation.hdbscan.hdbscan`: the exact
+mutual-reachability spanning tree on the GPU, `--min_cluster_size`, `--min_samples`) needs no `--k`, finds the number of clusters
+(printed; it is `pretrain.task_label`), copes with clusters of different density and labels the rest -1.  Those rows are written
+unless `--drop_unreached` is given (UnFuSeD needs 0 .. C - 1); `--confidence` adds the membership strength as a third column;
+`--score` scores the files that are in a cluster.  The reference has no counterpart.
 `--compare other.csv` prints the normalised mutual information between the labels just written and those of another
 `files,label` file over the same files (a k-means labeling against a PIC one, or pseudo-labels against real ones).
 `--score` prints the silhouette coefficient (sklearn's `silhouette_score`, Euclidean) of the labels just written on the whitened
@@ -125,6 +133,15 @@ def spread_labels(feats, rows, ids, classes, pca, nnn, sigma, alpha, iters=None)
     return xb, labels, res.confidence[:, 0].cpu().numpy()
 
 
+def write_labels_with_unreached(files, labels, conf, args):
+    """`files,label[,confidence]` to args.out for the algorithms that may leave a file without a label (-1): spread, hdbscan."""
+    with open(args.out, "w") as f:
+        f.write("files,label,confidence\n" if args.confidence else "files,label\n")
+        for p, l, c in zip(files, labels, conf):
+            if l >= 0 or not args.drop_unreached:
+                f.write(f"{p},{int(l)},{float(c):.6f}\n" if args.confidence else f"{p},{int(l)}\n")
+
+
 def main(args):
     from src.evaluation.embed import extract_embeddings, load_embedder
     if not torch.cuda.is_available():
@@ -158,13 +175,18 @@ def main(args):
         features, labels, conf = spread_labels(feats, seed_rows, seed_ids, len(names), pca, args.nnn, args.sigma, args.spread_alpha,
                                                args.spread_iters)
         unreached = int((labels < 0).sum())
-        with open(args.out, "w") as f:
-            f.write("files,label,confidence\n" if args.confidence else "files,label\n")
-            for p, l, c in zip(files, labels, conf):
-                if l >= 0 or not args.drop_unreached:
-                    f.write(f"{p},{int(l)},{float(c):.6f}\n" if args.confidence else f"{p},{int(l)}\n")
+        write_labels_with_unreached(files, labels, conf, args)
         print(f"{len(files)} files, {len(names)} classes from {len(seed_rows)} seeds, {unreached} unreached"
               f"{' (dropped)' if args.drop_unreached else ''}, spread sigma {args.sigma:g} nnn {args.nnn} alpha {args.spread_alpha:g} -> {args.out}")
+    elif args.clustering == "hdbscan":
+        from src.evaluation.hdbscan import hdbscan
+        features = preprocess_features(feats, pca=pca)
+        res = hdbscan(features, min_cluster_size=args.min_cluster_size, min_samples=args.min_samples)
+        labels, conf = res.labels, res.probabilities
+        noise = int((labels < 0).sum())
+        write_labels_with_unreached(files, labels, conf, args)
+        print(f"{len(files)} files, {res.n_clusters} clusters, {noise} noise{' (dropped)' if args.drop_unreached else ''}, hdbscan "
+              f"min_cluster_size {args.min_cluster_size} min_samples {args.min_samples} -> {args.out}")
     else:
         if args.k_sweep:
             model, loss, chosen = sweep_kmeans(feats, args.k_sweep, pca, verbose=args.verbose)
@@ -175,7 +197,12 @@ def main(args):
         print(f"{len(files)} files, {model.k} clusters, k-means loss {loss:.6g} -> {args.out}")
         features = model.features
     if args.score:
-        score, count, singles = _silhouette(features, labels)
+        if args.clustering == "hdbscan":                                 # noise is in no cluster: the files that are in one
+            inside = np.flatnonzero(labels >= 0)
+            score, count, singles = (_silhouette(features[torch.from_numpy(inside).to(features.device)], labels[inside])
+                                     if len(inside) else (None, 0, 0))
+        else:
+            score, count, singles = _silhouette(features, labels)
         print(f"silhouette {_fmt(score)} ({count} clusters, {singles} singletons)")
     if args.map:
         from src.evaluation.tsne import tsne
@@ -206,11 +233,11 @@ def _k_list(text):
 
 
 def get_args(argv=None):
-    parser = argparse.ArgumentParser(allow_abbrev=False, description="checkpoint -> embeddings -> k-means, PIC or seeded (label spreading) pseudo-labels")
+    parser = argparse.ArgumentParser(allow_abbrev=False, description="checkpoint -> embeddings -> k-means, PIC, seeded (label spreading) or HDBSCAN pseudo-labels")
     parser.add_argument("--checkpoint", type=str, required=True)
     parser.add_argument("--upstream", type=str, default="delores_m")
     parser.add_argument("--input", type=str, required=True, help="csv with a `files` column")
-    parser.add_argument("--clustering", choices=("kmeans", "pic", "spread"), default="kmeans")
+    parser.add_argument("--clustering", choices=("kmeans", "pic", "spread", "hdbscan"), default="kmeans")
     parser.add_argument("--k", type=int, default=None, help="number of clusters for k-means (the reference uses 585); ignored by pic")
     parser.add_argument("--k_sweep", type=_k_list, default=None,
                         help="k-means: comma-separated k values in place of --k; the k with the highest silhouette is written")
@@ -223,8 +250,10 @@ def get_args(argv=None):
     parser.add_argument("--seed_labels", type=str, default=None, help="spread: `files,label` csv of the labelled files (a subset of --input)")
     parser.add_argument("--spread_alpha", type=float, default=0.99, help="spread: share of a node's value that comes from its neighbours")
     parser.add_argument("--spread_iters", type=int, default=None, help="spread: rounds (default: until spread_alpha^iters <= 1e-3)")
-    parser.add_argument("--drop_unreached", action="store_true", help="spread: leave files no seed reaches out of --out")
-    parser.add_argument("--confidence", action="store_true", help="spread: a third column, 1 - H(p) / log C")
+    parser.add_argument("--drop_unreached", action="store_true", help="spread: leave files no seed reaches out of --out; hdbscan: the noise files")
+    parser.add_argument("--confidence", action="store_true", help="spread: a third column, 1 - H(p) / log C; hdbscan: the membership strength")
+    parser.add_argument("--min_cluster_size", type=int, default=25, help="hdbscan: the smallest group that counts as a cluster")
+    parser.add_argument("--min_samples", type=int, default=5, help="hdbscan: the neighbour (the file itself counted) whose distance is a file's core distance")
     parser.add_argument("--compare", type=str, default=None, help="another `files,label` csv: print the NMI against it")
     parser.add_argument("--score", action="store_true", help="print the silhouette coefficient of the labels just written")
     parser.add_argument("--map", type=str, default=None, help="`files,label,x,y` csv to write: a 2-D t-SNE map of the whitened features")
@@ -242,6 +271,13 @@ def get_args(argv=None):
         parser.error("--k_sweep takes the place of --k: give one of them")
     if args.k_sweep is not None and args.clustering == "pic":
         parser.error("--k_sweep is for k-means: pic finds the number of clusters itself")
+    if args.clustering == "hdbscan":
+        if args.k is not None or args.k_sweep is not None:
+            parser.error("--k and --k_sweep are for k-means: hdbscan finds the number of clusters itself")
+        if args.min_cluster_size < 2:
+            parser.error("--min_cluster_size must be at least 2")
+        if not 1 <= args.min_samples <= 65:
+            parser.error("--min_samples must be in 1 .. 65")
     if args.clustering == "spread":
         if args.k is not None or args.k_sweep is not None:
             parser.error("--k and --k_sweep are for k-means: spread takes its classes from --seed_labels")
@@ -251,8 +287,10 @@ def get_args(argv=None):
             parser.error("--spread_alpha must be in (0, 1)")
         if args.spread_iters is not None and args.spread_iters < 1:
             parser.error("--spread_iters must be positive")
-    elif args.seed_labels is not None or args.drop_unreached or args.confidence:
-        parser.error("--seed_labels, --drop_unreached and --confidence go with --clustering spread")
+    elif args.seed_labels is not None:
+        parser.error("--seed_labels goes with --clustering spread")
+    elif args.clustering != "hdbscan" and (args.drop_unreached or args.confidence):
+        parser.error("--seed_labels, --drop_unreached and --confidence go with --clustering spread (the last two also with hdbscan)")
     if args.clustering == "kmeans" and args.k is None and args.k_sweep is None:
         parser.error("the following arguments are required: --k")       # argparse's own wording for a required option
     return args

@@ -603,6 +603,28 @@ int audiossl_graph_components_workspace(int n, long* bytes);
 int audiossl_graph_components(const int* rowptr, const int* col, int n, long cap, int* label, int* count, void* workspace,
                               long workspace_bytes, void* stream);
 
+/* ---- exact minimum spanning tree of the complete mutual-reachability graph (csrc/mst.hip): the stage of HDBSCAN (Campello et al.
+ * 2013; sklearn.cluster.HDBSCAN) that a neighbour list cannot give - single linkage over every threshold at once.  The n x n
+ * matrix is never stored: Boruvka's algorithm, one pass over the Gram tiles per round, ceil(log2 n) rounds issued, every kernel of
+ * a round returning at once when one component is left.  The workspace is device memory that needs no clearing; two calls on the
+ * same inputs agree bit for bit (integer atomic minima only, no float atomics); nothing synchronises with the host.  EINVAL for a
+ * null pointer or a refused shape before any launch, EALIGN for x or a workspace that is not 16-byte aligned.
+ * mreach_mst_workspace (host): bytes for mreach_mst (norms, component arrays, per-(row, split) candidates), non-decreasing in each
+ *   argument: a workspace sized for a forced `splits` also serves splits = 0.  n >= 2, 0 <= splits <= 64.
+ * mreach_mst: x [n][d] row-major fp32, n >= 2, d % 4 == 0 (pad with zero columns), 4 <= d <= 4096; core2 [n] fp32 >= 0, or NULL for
+ *   all zeros (the plain Euclidean tree); inputs finite.  Edge weights w2_ij = max(d2_ij, core2_i, core2_j), d2_ij = max(0, (n_i +
+ *   n_j) - 2 g_ij): knn_graph_l2's and range_fill's arithmetic (fp32-input MFMA, an fmaf chain over d in index order, n_i = g_ii by
+ *   the same chain), so d2_ij == d2_ji bit for bit and a core2 taken from knn_graph_l2's d2 ties bit for bit with the matching
+ *   d2_ij.  Edges are compared by the strict total order (w2 bits, min(i, j), max(i, j)): the tree is unique however heavy the
+ *   ties (repeated rows, integer data, core distances that dominate), it is Kruskal's under that order, and it does not depend on
+ *   `splits` or on how the tiles are walked.  eu, ev [n - 1] int32 with eu < ev, ew2 [n - 1] fp32: the edges, rounds in order and
+ *   inside a round by the id of the component that chose the edge - deterministic, not sorted.  rounds [1] (may be NULL): the
+ *   number of Boruvka rounds that did work.  splits: 0 = the library chooses how many workgroups share one 64-row block's walk,
+ *   1..64 forces it (capped at the number of 128-row tiles). */
+int audiossl_mreach_mst_workspace(int n, int splits, long* bytes);
+int audiossl_mreach_mst(const float* x, int n, int d, const float* core2, int splits, int* eu, int* ev, float* ew2, int* rounds,
+                        void* workspace, long workspace_bytes, void* stream);
+
 /* ---- label spreading on the same graph (csrc/spread.hip): Zhou et al. 2004, sklearn's `LabelSpreading`; the reference has no
  * counterpart.  S = D^-1/2 W D^-1/2, F_0 = Y, F <- alpha S F + (1 - alpha) Y on an [n][m] block whose m columns are independent
  * problems (classes x trials of a low-shot evaluation).  No float atomics: two calls agree bit for bit, and a column's result
